@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — RCM reorder + CSR permute on a 100M-nnz power-law (RMAT) CSR (BASELINE config 3).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = RCMReorder::GetReorder on the device-resident CSR followed by
@@ -51,7 +51,33 @@ def parse():
                          "the Reorder -> Permute2D -> Convert pipeline)")
     ap.add_argument("--leg-timeout", type=float, default=300.0,
                     help="multi-rank runs: seconds the sharded legs may take before the headline is printed without them")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's order, row_ptr, col, "
+                         "val) as DIR/<name>.npy: see dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 19  # elements kept of an array that is larger: with its positions, at most 16 B each
+
+
+def dump_outputs(path, arrays):
+    """Writes each (name, tensor, bound) as path/<name>.npy: float32 where every value fits its 24-bit mantissa (the
+    integers are below `bound`), else float64.  An array of more than DUMP_SAMPLE elements is written as the values at
+    DUMP_SAMPLE fixed positions (seeded by the array's length, ascending), which go to path/<name>_index.npy (float64):
+    the same arguments give the same positions in every run.  Four arrays stay below 34 MB."""
+    os.makedirs(path, exist_ok=True)
+    for name, t, bound in arrays:
+        t = t.reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            at = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), at.astype(np.float64))
+            t = t[torch.from_numpy(at).to(t.device)]
+        a = t.cpu().numpy()
+        exact32 = a.dtype == np.float32 or (bound is not None and bound <= 1 << 24)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if exact32 else np.float64))
 
 
 def kernel_alg_bytes(name, n, nnz, stats, launches):
@@ -118,6 +144,9 @@ def main():
         step()
     barrier()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before anything else overwrites them
+        dump_outputs(args.dump_outputs, [("order", order, n), ("row_ptr", out[0], nnz), ("col", out[1], n),
+                                         ("val", out[2], None)])
     # ---- instrumented region: the same loop again, every kernel launch bracketed by HIP events on the
     # library's stream (sbx_profile_*), for the per-kernel roofline figures
     ops.profile_enable(True, dev)

@@ -11,6 +11,12 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# processes a test starts on the one GPU at once: the pytest process has the GPU open as well, and the suite keeps to
+# at most six processes with the GPU open at the same time
+GPU_CHILDREN = 5
+# bench.py ranks: torch.distributed.run's agent process is counted with them, and --no-cpp keeps every rank from
+# starting a child of its own on the GPU (the C++ host layer's legs)
+BENCH_RANKS = 4
 
 
 def _free_port():
@@ -164,68 +170,66 @@ def test_rccl_communicator_single_rank():
         comm.close()
 
 
-def test_bench_eight_ranks_on_one_gpu():
-    """bench.py --gpus 8 as the driver launches it (torch.distributed.run, 8 fresh processes), but over gloo with all
+def test_bench_multi_rank_on_one_gpu(tmp_path):
+    """bench.py --gpus N as the driver launches it (torch.distributed.run, N fresh processes), but over gloo with all
     ranks on GPU 0 and a small matrix: the perm broadcast, the per-rank regeneration, the nnz-balanced ranges, slab
-    sizing, both sharded legs through the C ABI and the watchdog all run with 8 ranks; the line must carry both legs
-    without an error."""
+    sizing, both sharded legs through the C ABI and the watchdog all run with N = BENCH_RANKS ranks; the line must
+    carry both legs without an error."""
     import json
     import subprocess
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected but no GPU is visible (the HIP path has no CPU fallback)")
     env = dict(os.environ, SBX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = _free_port()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--scale", "16", "--steps", "2",
-           "--warmup", "1", "--leg-timeout", "240"]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(BENCH_RANKS),
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(BENCH_RANKS),
+           "--scale", "16", "--steps", "2", "--warmup", "1", "--leg-timeout", "240", "--no-cpp"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:  # the ranks' own messages sit in front of torchrun's summary
         first = [l for l in r.stderr.splitlines() if "Error" in l or "error" in l or "sbx" in l][:40]
-        dump = os.path.join(ROOT, "gpurun_out", "bench8_stderr.log")
-        try:
-            os.makedirs(os.path.dirname(dump), exist_ok=True)
-            open(dump, "w").write(r.stderr)
-        except OSError:
-            pass
-        assert False, "\n".join(first) + "\n...\n" + r.stderr[-1500:]
+        dump = tmp_path / f"bench{BENCH_RANKS}_stderr.log"
+        dump.write_text(r.stderr)
+        assert False, "\n".join(first) + "\n...\n" + r.stderr[-1500:] + f"\n(whole stderr: {dump})"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 8 and line["value"] > 0
+    assert line["n_gpus"] == BENCH_RANKS and line["value"] > 0
     for leg in ("permute_apply", "convert_apply"):
         assert line[leg] is not None and "error" not in line[leg], line[leg]
     assert line["permute_apply"]["ranges"] == "nnz-balanced"
 
 
-def test_rcm_eight_processes_on_one_gpu():
-    """Eight processes ordering the same graphs on ONE GPU at once: the persistent kernels' grid barriers give up now and
-    then, workgroups of one launch get far apart in time — the results must stay the oracle's.  (Round 3: a workgroup
-    that was slow to read the cone list's counter behind a barrier walked a different range than the others, about one
-    call in a hundred ended in "not structurally symmetric"; fixed in k_ubfs_cone_run.)"""
+def test_rcm_concurrent_processes_on_one_gpu():
+    """GPU_CHILDREN processes ordering the same graphs on ONE GPU at once: the persistent kernels' grid barriers give up
+    now and then, workgroups of one launch get far apart in time — the results must stay the oracle's.  (Round 3: a
+    workgroup that was slow to read the cone list's counter behind a barrier walked a different range than the others,
+    about one call in a hundred ended in "not structurally symmetric"; fixed in k_ubfs_cone_run.)"""
     import subprocess
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected but no GPU is visible (the HIP path has no CPU fallback)")
     env = dict(os.environ, RCM_MODES_SMALL="1")
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "rcm_modes.py")], cwd=ROOT, env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for _ in range(8)]
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for _ in range(GPU_CHILDREN)]
     outs = [p.communicate(timeout=600)[0] for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-1500:]
 
 
-def test_rcm_eight_processes_thousands_of_calls():
-    """Eight processes, 400 rounds over four graphs each, on ONE GPU, every call trying the persistent kernels again
-    (SBX_DEBUG_GB_BACKOFF=0): 12 800 orderings against the oracle.  What this guards: a workgroup's stores for the other
-    workgroups — the small levels' queue entries and hub queue — have to arrive before its arrival at the grid barrier
-    is counted (gb_wait waits for them; `__syncthreads()` alone does not), or a workgroup on another XCD passes the
-    barrier and reads the old word.  With the memory side congested by the other processes that lost part of a level
+def test_rcm_concurrent_processes_thousands_of_calls():
+    """GPU_CHILDREN processes, 12 800 / GPU_CHILDREN / 4 rounds over four graphs each, on ONE GPU, every call trying the
+    persistent kernels again (SBX_DEBUG_GB_BACKOFF=0): 12 800 orderings against the oracle.  What this guards: a
+    workgroup's stores for the other workgroups — the small levels' queue entries and hub queue — have to arrive before
+    its arrival at the grid barrier is counted (gb_wait waits for them; `__syncthreads()` alone does not), or a workgroup
+    on another XCD passes the barrier and reads the old word.  With the memory side congested by the other processes that lost part of a level
     about once in 5000 calls — rounds 2 to 4 carried it."""
     import subprocess
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected but no GPU is visible (the HIP path has no CPU fallback)")
     env = dict(os.environ, SBX_DEBUG_GB_BACKOFF="0")
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "rcm_shared_loop.py"), "400"], cwd=ROOT, env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for _ in range(8)]
+    rounds = -(-12800 // (4 * GPU_CHILDREN))  # four orderings a round
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "rcm_shared_loop.py"), str(rounds)], cwd=ROOT,
+                              env=env,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for _ in range(GPU_CHILDREN)]
     outs = [p.communicate(timeout=900)[0] for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0 and "mismatches 0 exceptions 0" in o, o[-1500:]
