@@ -274,6 +274,21 @@ int sbx_csr_bandwidth(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz,
 int sbx_csr_profile(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
                     const void *col, int64_t *profile_host);
 
+/* sbx_csr_jaccard_weights — feature::JaccardWeights, feature/jaccard_weights_cuda.cu:99-150 (registered for the
+ * device CSR only, feature/jaccard_weights.cc:31-37).  One weight per nonzero of a square CSR whose rows have sorted
+ * columns, FeatureType float (feature_bytes 4) or double (8).  With deg(x) = row_ptr[x+1] - row_ptr[x], the entry at
+ * position p of row u with column v is
+ *   skipped  when deg(v) < deg(u), or deg(v) == deg(u) && v > u                                       (:126-129)
+ *   else     I = entries t of row u, with multiplicity, that the reference's search bst(v, t) finds in row v (:69-90,
+ *            :135-138); J = (float)I / (float)(deg(u) + deg(v) - I), correctly rounded fp32 (a double output holds
+ *            this float widened); weights_out[p] = J, and weights_out[bst(v, u)] = J when u occurs in row v (:142-146).
+ * Every position those writes miss (asymmetric patterns, duplicate entries the search does not land on), which the
+ * reference leaves uninitialised, gets the weight of its own (row, column) pair computed the same way.  Columns
+ * outside [0, n) read as rows without entries.  Degrees must be below 2^31 (else SBX_ERR_UNSUPPORTED).  Complete in
+ * stream order on the handle's stream, like sbx_csr_degree_distribution.                                           */
+int sbx_csr_jaccard_weights(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
+                            const void *col, int feature_bytes, void *weights_out);
+
 /* ------------------------------------------------------------------ *
  * A6  DegreeReorder::CalculateReorderCSR — reorder/degree_reorder.cc:22-62
  * inv_perm_out[old_row] = new_row; ascending: (deg asc, id desc),        *

@@ -275,6 +275,18 @@ def csr_profile(row_ptr, col):
     return out.value
 
 
+def csr_jaccard_weights(row_ptr, col, dtype=torch.float32):
+    """Jaccard weight of every nonzero of a square CSR graph with sorted rows (feature::JaccardWeights): a device
+    tensor of col.numel() float32 / float64 values, see sbx_csr_jaccard_weights in include/sbx.h for the rules."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"Jaccard weights are float32 or float64, not {dtype}")
+    out = torch.empty(col.numel(), dtype=dtype, device=row_ptr.device)
+    hd.check(hd.lib.sbx_csr_jaccard_weights(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, col.numel(), _p(row_ptr),
+                                            _p(col), out.element_size(), _p(out)))
+    return out
+
+
 # ----------------------------------------------------------------------------- reorderers
 def degree_reorder(row_ptr, ascending=True, out=None, id_dtype=None):
     hd = handle_for(_check_dev(row_ptr))
