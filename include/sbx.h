@@ -289,6 +289,30 @@ int sbx_csr_profile(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, c
 int sbx_csr_jaccard_weights(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
                             const void *col, int feature_bytes, void *weights_out);
 
+/* sbx_csr_triangle_count — feature::TriangleCount, feature/triangle_count.cc:142-223 (DirectedTriangleCount :142-175,
+ * UndirectedTriangleCount :178-206, GetTriangleCountCSR :209-223; countDirected = SBX_TC_DIRECTED).  A square CSR whose rows may be unsorted and hold
+ * duplicates and self loops; no mode assumes sorted columns.  Synchronous: *count_host is valid on return.
+ * Reference mode (flags without SBX_TC_EXACT) is the reference's value, which is not a triangle count: its marker
+ * array is written with the current vertex id and never cleared, so a mark made by vertex 0 reads as unset.  Counts
+ * run over stored entries with multiplicity:
+ *   undirected  first[w] = the smallest row u >= 1 holding an entry with column w (+inf if none); the count is the
+ *               number of entry pairs ((node, v) in row node, (v, w) in row v) with node < v < w and first[w] <= node.
+ *   directed    first[w] = the smallest column >= 1 among the entries of row w (+inf if none); the count is the number
+ *               of entry pairs ((node, v), (v, w)) with node < v, node < w and first[w] <= node.
+ * The reference loops over int: parity with it holds for n, nnz < 2^31; beyond that the rule is the definition.
+ * Exact mode (SBX_TC_EXACT):
+ *   undirected  the simple graph with an edge {a, b} for every entry (a, b), a != b (both directions and duplicates
+ *               merge); the count is the number of 3-vertex sets that are pairwise adjacent.
+ *   directed    the simple digraph with an arc a -> b for every entry (a, b), a != b (duplicates merge); the count is
+ *               the number of directed 3-cycles a -> b -> c -> a, each once (the two orientations of one vertex triple
+ *               are two cycles).
+ * In every mode a column outside [0, n) stands for a vertex with no entries that is never marked.  Limits
+ * (SBX_ERR_UNSUPPORTED): n >= 2^31; nnz >= 2^32 in reference mode, nnz >= 2^31 in exact mode.                       */
+#define SBX_TC_DIRECTED 0x1u /* TriangleCountParams::countDirected */
+#define SBX_TC_EXACT 0x2u    /* the true count instead of the reference's value */
+int sbx_csr_triangle_count(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
+                           const void *col, unsigned flags, int64_t *count_host);
+
 /* ------------------------------------------------------------------ *
  * A6  DegreeReorder::CalculateReorderCSR — reorder/degree_reorder.cc:22-62
  * inv_perm_out[old_row] = new_row; ascending: (deg asc, id desc),        *

@@ -15,6 +15,7 @@ SBX_OK = 0
 SBX_I32, SBX_I64, SBX_I32_N64 = 0, 1, 2
 V_NONE, V_I32, V_U32, V_F32, V_I64, V_U64, V_F64 = range(7)
 FLAG_MOVE, FLAG_ROWS_SORTED = 1, 2
+TC_DIRECTED, TC_EXACT = 1, 2
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -83,6 +84,7 @@ PROTOTYPES = {
     "sbx_csr_bandwidth": ([_H, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64)], _int),
     "sbx_csr_profile": ([_H, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64)], _int),
     "sbx_csr_jaccard_weights": ([_H, _int, _i64, _i64, _vp, _vp, _int, _vp], _int),
+    "sbx_csr_triangle_count": ([_H, _int, _i64, _i64, _vp, _vp, _u, C.POINTER(_i64)], _int),
     "sbx_degree_reorder": ([_H, _int, _i64, _vp, _int, _vp], _int),
     "sbx_rcm_reorder": ([_H, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(RcmStats)], _int),
     "sbx_gray_row_keys": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, C.POINTER(_i64)], _int),

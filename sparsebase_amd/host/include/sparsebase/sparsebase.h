@@ -11,6 +11,7 @@
 #include "sparsebase/feature/degree_distribution.h"
 #include "sparsebase/feature/degrees.h"
 #include "sparsebase/feature/jaccard_weights.h"
+#include "sparsebase/feature/triangle_count.h"
 #include "sparsebase/feature/profile.h"
 #include "sparsebase/format/coo.h"
 #include "sparsebase/format/csc.h"

@@ -287,6 +287,19 @@ def csr_jaccard_weights(row_ptr, col, dtype=torch.float32):
     return out
 
 
+def csr_triangle_count(row_ptr, col, directed=False, exact=False):
+    """feature::TriangleCount of a square CSR graph, an int.  exact=False is the reference's value (which is not the
+    number of triangles: a 4-cycle 1-2-3-4 gives 1, a triangle 0-1-2 gives 0); exact=True counts the triangles of the
+    simple undirected graph, or with directed=True the directed 3-cycles.  See sbx_csr_triangle_count in
+    include/sbx.h for the rules."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    out = C.c_int64(0)
+    flags = (capi.TC_DIRECTED if directed else 0) | (capi.TC_EXACT if exact else 0)
+    hd.check(hd.lib.sbx_csr_triangle_count(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, col.numel(), _p(row_ptr),
+                                           _p(col), flags, C.byref(out)))
+    return out.value
+
+
 # ----------------------------------------------------------------------------- reorderers
 def degree_reorder(row_ptr, ascending=True, out=None, id_dtype=None):
     hd = handle_for(_check_dev(row_ptr))
