@@ -1475,6 +1475,19 @@ extern "C" int sbx_gray_row_keys(sbx_handle_t h, sbx_index_type it, int64_t n, i
 }
 #endif
 
+// the paths the keys take by default, switched off in A/B variant builds (tools/build_variant.py ... -DNAME=0): the
+// short-row fast path (else the general tile kernel), the banded kernel's attempt, the one-kernel form for rows of up to
+// GR_TINY entries
+#ifndef SBX_GRAY_SHORT_ROWS
+#define SBX_GRAY_SHORT_ROWS 1
+#endif
+#ifndef SBX_GRAY_BANDED_FIRST
+#define SBX_GRAY_BANDED_FIRST 1
+#endif
+#ifndef SBX_GRAY_TINY_ROWS
+#define SBX_GRAY_TINY_ROWS 1
+#endif
+
 int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void *row_ptr, const void *col, int resolution,
                    int nnz_threshold, void *degree_out, uint64_t *key_out, int64_t *counts_host) {
   int bits = resolution;
@@ -1521,13 +1534,12 @@ int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
     unsigned *nlong = &both->nlong;
     int32_t *long_list = nullptr;
     SBX_TRY(sbx_salloc(h, (size_t)GR_LONG_LIST, &long_list));
-    static const bool allow = !(sbx_env_tuning("SBX_GRAY_SHORT_ROWS") && atoi(sbx_env_tuning("SBX_GRAY_SHORT_ROWS")) == 0);
     const unsigned hmax = (unsigned)GR_SHORT_MAX;  // bound of the rows the kernel handles
     // a row of d <= hmax entries compares its block counts with d / resolution <= hmax / resolution: that many
     // saturating counter slices + 1.  The kernel is built for up to 5 (resolution >= 16) — what the tests of round 2
     // missed and tools/fuzz_ops.py found: below that the tile kernel does the work
     const int lv = (int)(hmax >= (unsigned)bits && (int)hmax > nnz_threshold ? hmax / (unsigned)bits : 0u) + 1;
-    if (allow && lv <= (bits <= 32 ? 5 : 2) && nnz >= 4) {  // (gr_load4 reads 16 bytes at a clamped address)
+    if (SBX_GRAY_SHORT_ROWS && lv <= (bits <= 32 ? 5 : 2) && nnz >= 4) {  // (gr_load4 reads 16 bytes at a clamped address)
       const unsigned grid = sbx_grid_for(n, 256 / GR_LPR, (int64_t)h->num_cus * 16);
       int wshift = -1;
       if ((width & (width - 1)) == 0)
@@ -1554,7 +1566,6 @@ int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
       else GRAY_ROWS(K, GRID, unsigned long long, 2, ##__VA_ARGS__); /* 64 blocks: thr <= 64 / 64 */               \
     }                                                                                                              \
   } while (0)
-      static const bool try_banded = !(sbx_env_tuning("SBX_GRAY_BANDED_FIRST") && atoi(sbx_env_tuning("SBX_GRAY_BANDED_FIRST")) == 0);
       GrayBoth hb;
       hb.nlong = 0, hb.pad = GR_POWER_LAW;
       // the counters (what the later kernels of the banded path added) + k_gray_rows_short's GR_EARLY copies, summed here
@@ -1569,7 +1580,7 @@ int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
         }
         return SBX_OK;
       };
-      if (try_banded) {
+      if (SBX_GRAY_BANDED_FIRST) {
         GRAY_ROWS_BY_LEVELS(k_gray_rows_short, grid);
         SBX_LAUNCH_CHECK(h);
         // one read-back: how many long rows the kernel met and — final if there were none — the band counters
@@ -1608,9 +1619,8 @@ int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
         GrayCounts *spread = all->spread;
         const int64_t brows = (int64_t)GB_ITERS * 4 * GB_GROUPS * 64;  // rows per workgroup
         const unsigned bgrid = (unsigned)((n + brows - 1) / brows);
-        static const bool tiny_on = !(sbx_env_tuning("SBX_GRAY_TINY_ROWS") && atoi(sbx_env_tuning("SBX_GRAY_TINY_ROWS")) == 0);
         // (a row of up to GR_TINY entries has threshold 0 when it is shorter than `resolution` or not above the nnz threshold)
-        if (tiny_on && (bits > GR_TINY || nnz_threshold >= GR_TINY)) {
+        if (SBX_GRAY_TINY_ROWS && (bits > GR_TINY || nnz_threshold >= GR_TINY)) {
           int32_t *mid_list = nullptr;
           SBX_TRY(sbx_salloc(h, (size_t)n, &mid_list));
 #define GRAY_TINY(B)                                                                                                  \

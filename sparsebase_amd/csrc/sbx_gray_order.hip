@@ -155,11 +155,6 @@ __global__ __launch_bounds__(256) void k_go_widen(const uint32_t *__restrict__ i
   for (; i < n; i += stride) out[i] = (I)in[i];
 }
 
-static bool gray_three_sorts() {  // SBX_GRAY_ORDER_THREE_SORTS=1: the ordering keeps its three sorts whatever the parameters (tests, A/B)
-  static const bool on = sbx_env_test("SBX_GRAY_ORDER_THREE_SORTS") && atoi(sbx_env_test("SBX_GRAY_ORDER_THREE_SORTS")) != 0;
-  return on;
-}
-
 template <typename I>
 int gray_order_one_sort(sbx_handle_t h, int64_t n, const I *deg, const uint64_t *gkey, bool sparse_banded, bool dense_banded,
                         int kbits, int dbits, int cbits, uint32_t dense_class, int64_t dmax, int64_t thr, int group_size,
@@ -236,7 +231,7 @@ int gray_order_typed(sbx_handle_t h, int64_t n, int64_t nnz, const I *deg, const
     const uint32_t dense_class_1 = sparse_banded ? 1u : (uint32_t)((dmax + gs - 1) / gs) + 1u;
     const int cbits = sbx_bits_for((uint64_t)dense_class_1), dbits1 = sbx_bits_for((uint64_t)dmax);
     const int kbits = (sparse_banded && dense_banded) ? 0 : bits;
-    if (cbits + kbits + dbits1 <= 64 && !gray_three_sorts())
+    if (cbits + kbits + dbits1 <= 64 && !sbx_sw().gray_three_sorts)
       return gray_order_one_sort<I>(h, n, deg, gkey, sparse_banded, dense_banded, kbits, dbits1, cbits, dense_class_1, dmax,
                                     thr, (int)gs, bits >= 64 ? ~0ull : ((1ull << bits) - 1ull), inv_out);
   }

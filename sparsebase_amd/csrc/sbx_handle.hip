@@ -4,10 +4,69 @@
 // converter/converter_cuda.cu:12-21) behind the C ABI of include/sbx.h.
 #include "sbx_internal.h"
 
+#include <algorithm>
 #include <new>
 
 static const size_t kArenaAlign = 256;
 static const size_t kPinnedBytes = 1 << 16;
+
+#ifndef SBX_READBACK_POLL
+#define SBX_READBACK_POLL 1  // 0: small device->host results through hipMemcpyAsync + hipStreamSynchronize (sbx_readback)
+#endif
+
+// The environment switches (sbx_switches in sbx_internal.h), each parsed as it always was.  The function-local static is
+// initialised once per process, thread-safely.
+const sbx_switches &sbx_sw() {
+  static const sbx_switches sw = [] {
+    auto on_unless_0 = [](const char *name) {  // on unless set to 0
+      const char *e = getenv(name);
+      return !(e && atoi(e) == 0);
+    };
+    auto off_unless_set = [](const char *name) {  // off unless set to a non-zero number
+      const char *e = getenv(name);
+      return e && atoi(e) != 0;
+    };
+    auto present = [](const char *name) { return getenv(name) != nullptr; };
+    auto integer = [](const char *name, long long dflt) {
+      const char *e = getenv(name);
+      return e ? atoll(e) : dflt;
+    };
+    auto real = [](const char *name, double dflt) {
+      const char *e = getenv(name);
+      return e ? atof(e) : dflt;
+    };
+    sbx_switches w;
+    w.rcm_split_expand = on_unless_0("SBX_RCM_SPLIT_EXPAND");
+    w.rcm_cc_overlap = on_unless_0("SBX_RCM_CC_OVERLAP");
+    w.rcm_overlap = on_unless_0("SBX_RCM_OVERLAP");
+    w.rcm_count_sort = on_unless_0("SBX_RCM_COUNT_SORT");
+    w.rcm_ranked_keys = on_unless_0("SBX_RCM_RANKED_KEYS");
+    w.rcm_unordered = on_unless_0("SBX_RCM_UNORDERED");
+    const int chain = (int)integer("SBX_RCM_UBFS_CHAIN", 3);
+    w.rcm_ubfs_chain = chain < 0 ? 0 : (chain > 8 ? 8 : chain);
+    w.rcm_tie_walk = on_unless_0("SBX_RCM_TIE_WALK");
+    w.rcm_tie_spec = on_unless_0("SBX_RCM_TIE_SPEC");
+    w.rcm_head_chain = on_unless_0("SBX_RCM_HEAD_CHAIN");
+    w.bu_ratio = real("SBX_DEBUG_BU_RATIO", 4.0);
+    w.gb_backoff = (int)integer("SBX_DEBUG_GB_BACKOFF", 16);
+    w.gb_spins = (unsigned)integer("SBX_DEBUG_GB_SPINS", GB_SPINS);
+    const int div = (int)integer("SBX_DEBUG_RCM_RANKED_DIV", 3);
+    w.rcm_ranked_div = div > 0 ? div : 1;
+    w.ub_max_levels = (unsigned)integer("SBX_DEBUG_UB_MAX_LEVELS", 64);
+    w.tie_edges = std::min((unsigned)integer("SBX_DEBUG_TIE_EDGES", TS_EDGES), TS_EDGES);
+    w.tie_single = std::min((unsigned)integer("SBX_DEBUG_TIE_SINGLE", TS_SINGLE), TS_SINGLE);
+    w.tie_cap = std::min((unsigned)integer("SBX_DEBUG_TIE_CAP", TS_CAP), TS_CAP);
+    w.tie_walk_debug = present("SBX_DEBUG_TIE_WALK");
+    w.rcm_check = off_unless_set("SBX_DEBUG_RCM_CHECK");
+    w.chain_tail_abort = off_unless_set("SBX_DEBUG_CHAIN_TAIL_ABORT");
+    w.permute_overlap = on_unless_0("SBX_PERMUTE_OVERLAP");
+    w.permute_force_radix = integer("SBX_PERMUTE_FORCE_RADIX", 0) & 1;
+    w.permute_no_tile2 = present("SBX_PERMUTE_NO_TILE2");
+    w.gray_three_sorts = off_unless_set("SBX_GRAY_ORDER_THREE_SORTS");
+    return w;
+  }();
+  return sw;
+}
 
 extern "C" int sbx_version(void) { return SBX_VERSION; }
 
@@ -105,10 +164,6 @@ extern "C" int sbx_create(int device, sbx_handle_t *out) {
   h->rs_next = 0;
   h->oom_hook = nullptr;
   h->oom_user = nullptr;
-  {
-    const char *e = sbx_env_tuning("SBX_READBACK_POLL");
-    h->rb_poll = !(e && e[0] == '0');
-  }
   memset(h->pinned, 0, kPinnedBytes);
   *out = h;
   return SBX_OK;
@@ -305,7 +360,7 @@ __global__ void k_readback(unsigned *__restrict__ dst, const unsigned *__restric
 int sbx_readback(sbx_handle_t h, void *dst_host, const void *src_dev, size_t bytes) {
   if (bytes + kReadbackHeader > h->pinned_bytes) SBX_FAIL(h, SBX_ERR_INTERNAL, "readback of %zu bytes too large", bytes);
   char *payload = (char *)h->pinned + kReadbackHeader;
-  if (!h->rb_poll || (bytes & 3) || ((uintptr_t)src_dev & 3)) {
+  if (!SBX_READBACK_POLL || (bytes & 3) || ((uintptr_t)src_dev & 3)) {
     SBX_HIP(h, hipMemcpyAsync(payload, src_dev, bytes, hipMemcpyDeviceToHost, h->stream));
     SBX_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(dst_host, payload, bytes);

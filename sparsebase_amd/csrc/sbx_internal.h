@@ -75,7 +75,6 @@ struct sbx_handle_s {
   int rs_next;
   void *pow5;       // device table of 5^k for the exact decimal conversion (sbx_mtx.hip), built on first use
   unsigned rb_seq;  // sequence number of the last polled read-back (sbx_readback)
-  bool rb_poll;     // SBX_READBACK_POLL=0 selects the copy-engine path
   sbx_oom_hook oom_hook;  // asked once when a device allocation of the library's own fails (sbx_set_oom_hook)
   void *oom_user;
   int rcm_gb_backoff;  // RCM calls left to run without the persistent (grid-barrier) kernels after one of them gave up
@@ -163,20 +162,49 @@ int sbx_radix_slot(sbx_handle_t h, void **slot);
 int sbx_readback(sbx_handle_t h, void *dst_host, const void *src_dev, size_t bytes);
 
 // ---- environment switches ------------------------------------------------------------------------------------------------
-// Two kinds.  sbx_env_test(): what the test-suite needs to reach a code path that production takes only under conditions a
-// test cannot arrange (a grid barrier giving up, a level beyond a size limit, every row on the radix fallback) — always
-// read; every one of them selects code that also runs without the switch.  sbx_env_tuning(): tuning ranges and
-// diagnostics — read only in builds with -DSBX_TUNING (python -m sparsebase_amd.build --tuning -> libsbx_tuning.so); the
-// product library does not look at them.
-static inline const char *sbx_env_test(const char *name) { return getenv(name); }
-static inline const char *sbx_env_tuning(const char *name) {
-#ifdef SBX_TUNING
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
+// What the test-suite needs to reach a code path that production takes only under conditions a test cannot arrange (a
+// grid barrier giving up, a level beyond a size limit, every row on the radix fallback).  Every switch selects code that
+// also runs without it.  sbx_sw() (sbx_handle.hip, the library's one reader of the environment) fills the table on first
+// use: once per process.  Tuning constants and timing ablations are compile-time macros instead (#ifndef NAME / #define
+// NAME <default> where they are used), set in a variant build: tools/build_variant.py <name> <file.hip> -DNAME=...
+
+// limits of RCM's tie walk (sbx_rcm.hip: k_ubfs_ties_small) and polls a grid barrier waits: the defaults of the switches
+// that lower them
+constexpr unsigned TS_CAP = 1024, TS_EDGES = 1u << 17;
+constexpr unsigned TS_SINGLE = 1u << 13;  // entries of a smallest-member step the one workgroup still scans itself
+constexpr unsigned GB_SPINS = 1u << 16;
+
+struct sbx_switches {
+  // RCM (sbx_rcm.hip, sbx_rcm64.hip)
+  bool rcm_split_expand;     // SBX_RCM_SPLIT_EXPAND, on; 0: a wide frontier's light rows are expanded in line
+  bool rcm_cc_overlap;       // SBX_RCM_CC_OVERLAP, on; 0: the labelling of the other components runs in line
+  bool rcm_overlap;          // SBX_RCM_OVERLAP, on; 0: the degree ranks run in line instead of on a side stream
+  bool rcm_count_sort;       // SBX_RCM_COUNT_SORT, on; 0: levels above 4096 vertices take the generic radix sort
+  bool rcm_ranked_keys;      // SBX_RCM_RANKED_KEYS, on; 0: big Cuthill-McKee levels sort full (parent position, rank) keys
+  bool rcm_unordered;        // SBX_RCM_UNORDERED, on; 0: every sweep of the search keeps the order inside its levels
+  int rcm_ubfs_chain;        // SBX_RCM_UBFS_CHAIN, 3 (clamped to 0 ... 8); 0: unordered sweeps run the per-level loop
+  bool rcm_tie_walk;         // SBX_RCM_TIE_WALK, on; 0: every tie-break through the persistent cone kernels
+  bool rcm_tie_spec;         // SBX_RCM_TIE_SPEC, on; 0: the host reads back behind every tie walk before the next sweep
+  bool rcm_head_chain;       // SBX_RCM_HEAD_CHAIN, on; 0: a read-back between the first sweep's head run and its chain
+  double bu_ratio;           // SBX_DEBUG_BU_RATIO, 4: frontier / unvisited edges above which an ordered level goes bottom-up
+  int gb_backoff;            // SBX_DEBUG_GB_BACKOFF, 16: calls kept off the persistent kernels after a barrier gave up
+  unsigned gb_spins;         // SBX_DEBUG_GB_SPINS, GB_SPINS: polls a grid barrier waits before it gives up (tests: 0)
+  int rcm_ranked_div;        // SBX_DEBUG_RCM_RANKED_DIV, 3 (at least 1): ranked keys from levels of n_ranked / this
+  unsigned ub_max_levels;    // SBX_DEBUG_UB_MAX_LEVELS, 64: deeper sweeps fall back to the ordered kind
+  unsigned tie_edges;        // SBX_DEBUG_TIE_EDGES, TS_EDGES (at most): the tie walk's edge limit, lowered
+  unsigned tie_single;       // SBX_DEBUG_TIE_SINGLE, TS_SINGLE (at most): entries above which a step goes to the grid
+  unsigned tie_cap;          // SBX_DEBUG_TIE_CAP, TS_CAP (at most): members of a level the tie walk takes
+  bool tie_walk_debug;       // SBX_DEBUG_TIE_WALK, off; set at all: the walk's exit is printed, no speculative sweep
+  bool rcm_check;            // SBX_DEBUG_RCM_CHECK, off; non-zero: every unordered sweep is checked, its trace printed
+  bool chain_tail_abort;     // SBX_DEBUG_CHAIN_TAIL_ABORT, off; non-zero: a chain's tail run gives up at once
+  // Permute2D and CSR row sort (sbx_permute.hip)
+  bool permute_overlap;      // SBX_PERMUTE_OVERLAP, on; 0: tile, block-row and long-row paths back to back on one stream
+  bool permute_force_radix;  // SBX_PERMUTE_FORCE_RADIX, off; bit 0 set: every tile / row takes the radix path
+  bool permute_no_tile2;     // SBX_PERMUTE_NO_TILE2, off; set at all: k_permute_tile where k_permute_tile2 would run
+  // Gray ordering (sbx_gray_order.hip)
+  bool gray_three_sorts;     // SBX_GRAY_ORDER_THREE_SORTS, off; non-zero: three sorts even where one 64-bit key does
+};
+const sbx_switches &sbx_sw();
 
 static inline int sbx_value_bytes(sbx_value_type vt) {
   switch (vt) {

@@ -657,15 +657,36 @@ __device__ __forceinline__ unsigned scan_bucket_counts(unsigned *c, int nc, unsi
   return mx;
 }
 
+// Timing ablations, for variant builds only (tools/build_variant.py <name> sbx_permute.hip -D...): they produce WRONG
+// matrices.  SBX_PERMUTE_ABLATE is a set of bits, in the tile, block-row and row-class kernels: bit 1 (2) rows stream out
+// unsorted, bit 2 (4) no relabel gathers, bit 3 (8) the row-class kernels always take level 1.  k_permute_tile and
+// k_permute_block_rows test them at compile time; k_rows_quad finds them in its force_radix argument next to the test bit
+// (compiled away there they cost it up to 22 VGPRs and some scratch).  SBX_DEBUG_TILE_STOP=k: k_permute_tile leaves
+// behind phase k (1 ... 5); 9: it stamps its phases instead (g_tile_stamps, printed by sort_stage).
+#ifndef SBX_PERMUTE_ABLATE
+#define SBX_PERMUTE_ABLATE 0
+#endif
+#ifndef SBX_DEBUG_TILE_STOP
+#define SBX_DEBUG_TILE_STOP 0
+#endif
+constexpr int PERMUTE_ABLATE = SBX_PERMUTE_ABLATE, TILE_STOP = SBX_DEBUG_TILE_STOP;
+static_assert((PERMUTE_ABLATE & ~0xE) == 0, "SBX_PERMUTE_ABLATE: bits 1 - 3");
+constexpr bool PERMUTE_ABLATING = PERMUTE_ABLATE != 0 || TILE_STOP != 0;  // (k_permute_tile2 has none of them)
+#ifndef SBX_DEBUG_LONG
+#define SBX_DEBUG_LONG 0  // 1: the long-row segment path prints what it did (long_rows_path)
+#endif
+
 // diagnostic only (SBX_DEBUG_TILE_STOP=9): wall-clock cycles from kernel entry to the end of each phase, summed over
 // the tiles by thread 0; [31] counts the tiles.  Printed and cleared by sort_stage.
 __device__ unsigned long long g_tile_stamps[32];
 #define TILE_STAMP(i)                                                                    \
   do {                                                                                   \
-    if (dbg_stop == 9 && tid == 0) {                                                     \
-      unsigned long long t_;                                                             \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");         \
-      atomicAdd(&g_tile_stamps[i], t_ - t_start);                                        \
+    if constexpr (dbg_stop == 9) {                                                       \
+      if (tid == 0) {                                                                    \
+        unsigned long long t_;                                                           \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");       \
+        atomicAdd(&g_tile_stamps[i], t_ - t_start);                                      \
+      }                                                                                  \
     }                                                                                    \
   } while (0)
 
@@ -716,10 +737,9 @@ __device__ __forceinline__ void permute_tile_body(
   // output index of entry k (position p): the row's start in the output + the entry's position inside the row
 #define OUTPOS(k, p) ((int64_t)s_ob[hl[k] & 0xFFFFu] + ((p) - (int)(hl[k] & 0xFFFFu)))
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int dbg_stop = force_radix >> 8;  // timing ablation only (SBX_DEBUG_TILE_STOP): leave after a phase, output junk
-  force_radix &= 0xFF;
+  constexpr int dbg_stop = RADIX ? 0 : TILE_STOP, ablate = RADIX ? 0 : PERMUTE_ABLATE;  // (timing ablations: see above)
   unsigned long long t_start = 0;
-  if (dbg_stop == 9) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_start)::"memory");
+  if constexpr (dbg_stop == 9) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_start)::"memory");
 
   // the tile's rows: those of at most PT_LMAX entries whose range in the SHORT-row entry space (prefix sums `sp`
   // over the lengths of such rows only) starts in the window; longer rows between them belong to other kernels
@@ -730,7 +750,7 @@ __device__ __forceinline__ void permute_tile_body(
   const int cnt = (int)((int64_t)in.e1 - e0);
   if (cnt == 0) return;
   TILE_STAMP(0);
-  if (dbg_stop == 9 && tid == 0) {
+  if constexpr (dbg_stop == 9) if (tid == 0) {
     atomicAdd(&g_tile_stamps[31], 1ull);
     atomicAdd(&g_tile_stamps[30], (unsigned long long)cnt);
   }
@@ -822,7 +842,7 @@ __device__ __forceinline__ void permute_tile_body(
   }
   TILE_SYNC();
   TILE_STAMP(3);
-  if (dbg_stop == 1) {
+  if constexpr (dbg_stop == 1) {
     for (int p = tid; p < cnt; p += THREADS) col_out[(int64_t)s_ob[s_hl[p] & 0xFFFFu] + (p - (int)(s_hl[p] & 0xFFFFu))] = (I)(s_a[p] + (int)s_hl[p]);
     return;
   }
@@ -848,7 +868,7 @@ __device__ __forceinline__ void permute_tile_body(
         if (HASV) kv[k] = __builtin_nontemporal_load((const V *)val_in + s);
       }
     }
-    if (dbg_stop == 9) {
+    if constexpr (dbg_stop == 9) {
       int acc = 0;
 #pragma unroll
       for (int k = 0; k < ITEMS; k++) acc += (int)c[k];
@@ -865,7 +885,7 @@ __device__ __forceinline__ void permute_tile_body(
     if constexpr (ITEMS == 8) asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4 % ITEMS]), "+v"(c[5 % ITEMS]), "+v"(c[6 % ITEMS]), "+v"(c[7 % ITEMS]));
     else asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
 #pragma unroll
-    for (int k = 0; k < ITEMS; k++) kc[k] = (int)((col_order && !(force_radix & 4)) ? col_order[c[k]] : c[k]);  // (bit 2: timing ablation without the gathers)
+    for (int k = 0; k < ITEMS; k++) kc[k] = (int)((col_order && !(ablate & 4)) ? col_order[c[k]] : c[k]);  // (bit 2: timing ablation without the gathers)
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
       const int p = k * THREADS + tid;
@@ -875,7 +895,7 @@ __device__ __forceinline__ void permute_tile_body(
   }
   TILE_SYNC();
   TILE_STAMP(5);
-  if (dbg_stop == 2) {
+  if constexpr (dbg_stop == 2) {
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
       const int p = k * THREADS + tid;
@@ -898,7 +918,7 @@ __device__ __forceinline__ void permute_tile_body(
           *(uint2 *)&s_c[2 * p] = make_uint2(0xFFFFFFFFu, 0u);
       }
     }
-    if (__any(unsorted) && lane == 0 && !(force_radix & 2)) {  // (bit 1: timing ablation, rows stream out unsorted)
+    if (__any(unsorted) && lane == 0 && !(ablate & 2)) {  // (bit 1: timing ablation, rows stream out unsorted)
       st->any_unsorted = 1;
       s_flag[0] = 1;
     }
@@ -990,7 +1010,7 @@ __device__ __forceinline__ void permute_tile_body(
   }
   TILE_SYNC();  // the (min, max) words and the column copies in r0 have been read
   TILE_STAMP(8);
-  if (dbg_stop == 3) {
+  if constexpr (dbg_stop == 3) {
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
       const int p = k * THREADS + tid;
@@ -1045,7 +1065,7 @@ __device__ __forceinline__ void permute_tile_body(
     if (tid == 0) s_flag[1] = 1;
     TILE_SYNC();
   }
-  if (dbg_stop == 4) {
+  if constexpr (dbg_stop == 4) {
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
       const int p = k * THREADS + tid;
@@ -1074,7 +1094,7 @@ __device__ __forceinline__ void permute_tile_body(
         fin[k] = (int)(b0 + r);
       }
     }
-    if (dbg_stop == 5) {
+    if constexpr (dbg_stop == 5) {
 #pragma unroll
       for (int k = 0; k < ITEMS; k++) {
         const int p = k * THREADS + tid;
@@ -1142,7 +1162,7 @@ __device__ __forceinline__ void permute_tile_body(
     }
     if (__any(dup) && lane == 0) st->any_dup = 1;
   }
-  if (dbg_stop == 9) {
+  if constexpr (dbg_stop == 9) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TILE_STAMP(15);
   }
@@ -1723,7 +1743,7 @@ __global__ __launch_bounds__(BR_THREADS) void k_permute_block_rows(
     }
     // B: relabel gathers of row it - 3 (permute_order_two.cc:68)
     int k_b[ITEMS];
-    if (col_order && !(force_radix & 4)) {  // (bit 2: timing ablation without the relabel gathers)
+    if (col_order && !(PERMUTE_ABLATE & 4)) {  // (bit 2: timing ablation without the relabel gathers)
 #pragma unroll
       for (int k = 0; k < ITEMS; k++) k_b[k] = (int)col_order[k * BR_THREADS + tid < len_b ? c_b[k] : 0];
     } else {
@@ -1761,7 +1781,7 @@ __global__ __launch_bounds__(BR_THREADS) void k_permute_block_rows(
           s_mm[2 * w] = mn;
           s_mm[2 * w + 1] = mx;
         }
-        if (__any(unsorted) && lane == 0 && !(force_radix & 2)) {  // (bit 1: timing ablation, rows stream out unsorted)
+        if (__any(unsorted) && lane == 0 && !(PERMUTE_ABLATE & 2)) {  // (bit 1: timing ablation, rows stream out unsorted)
           st->any_unsorted = 1;
           s_flag[0] = 1;
         }
@@ -2470,26 +2490,10 @@ int launch_fix(sbx_handle_t h, sbx_value_type vt, const I *rpo, const I *col, vo
   return SBX_OK;
 }
 
-static bool permute_overlap() {
-  static const bool on = !(sbx_env_test("SBX_PERMUTE_OVERLAP") && atoi(sbx_env_test("SBX_PERMUTE_OVERLAP")) == 0);
-  return on;
-}
-
-static int permute_grid_factor() {  // SBX_PERMUTE_GRID_FACTOR: workgroups launched per resident slot (tuning)
-  static const int f = sbx_env_tuning("SBX_PERMUTE_GRID_FACTOR") ? atoi(sbx_env_tuning("SBX_PERMUTE_GRID_FACTOR")) : 1;
-  return f < 1 ? 1 : f;
-}
-
-// SBX_PERMUTE_FORCE_RADIX=1: every tile / row takes the radix path (tests; a path production takes for clustered columns).
-// The timing ablations — bits 1 - 3 of the same variable (rows stream out unsorted / no relabel gathers / ...) and
-// SBX_DEBUG_TILE_STOP (leave the tile kernel behind phase k) — produce WRONG matrices and exist in the tuning build only.
-static int permute_force_radix() {
-  static const int on =
-      (sbx_env_test("SBX_PERMUTE_FORCE_RADIX") ? atoi(sbx_env_test("SBX_PERMUTE_FORCE_RADIX")) & 0x01 : 0) |
-      (sbx_env_tuning("SBX_PERMUTE_FORCE_RADIX") ? atoi(sbx_env_tuning("SBX_PERMUTE_FORCE_RADIX")) & 0xFE : 0) |
-      (sbx_env_tuning("SBX_DEBUG_TILE_STOP") ? atoi(sbx_env_tuning("SBX_DEBUG_TILE_STOP")) << 8 : 0);
-  return on;
-}
+#ifndef SBX_PERMUTE_GRID_FACTOR
+#define SBX_PERMUTE_GRID_FACTOR 1  // workgroups of the row classes launched per resident slot
+#endif
+constexpr unsigned PERMUTE_GRID_FACTOR = SBX_PERMUTE_GRID_FACTOR < 1 ? 1 : SBX_PERMUTE_GRID_FACTOR;
 
 // SBX_PERMUTE_ROW_WAVES: resident waves per CU the grids of the row classes up to 2048 entries are sized for.  Measured on
 // the bench matrix (tools/kt_rowwaves.sh; classes of 256 + 512 + 1024 slots): with a random order 8 / 12 / 16 waves per
@@ -2503,29 +2507,33 @@ static int permute_force_radix() {
 // persistent kernels that all run at once fight for the CUs' LDS and wave slots — and fewer streams are a coin toss:
 // all classes on one stream 1.32 / 1.49 ms (random / RCM order) on one box and 1.34 / 1.44 on another, where the six
 // streams below gave 1.31 / 1.42 and 1.35 / 1.46; big and small classes on two streams 1.34 / 1.40 and 1.40 / 1.50
-// (tools/permute_streams.sh).  Left at one stream per class.  SBX_PERMUTE_CLASS_STREAMS: six digits, class 0 ... 5.
-static int class_stream(int cls) {
-  static int map[BR_CLASSES] = {-1};
-  if (map[0] < 0) {
-    const char *e = sbx_env_tuning("SBX_PERMUTE_CLASS_STREAMS");
-    const char *d = (e && strlen(e) == BR_CLASSES) ? e : "023456";
+// (tools/permute_streams.sh).  Left at one stream per class.  SBX_PERMUTE_CLASS_STREAMS: six digits, class 0 ... 5 (an
+// invalid digit, 1 or beyond the side streams, means 0; a string of another length, the default).
+#ifndef SBX_PERMUTE_CLASS_STREAMS
+#define SBX_PERMUTE_CLASS_STREAMS "023456"
+#endif
+struct ClassStreams {
+  int s[BR_CLASSES];
+  constexpr ClassStreams() : s() {
+    constexpr const char *e = SBX_PERMUTE_CLASS_STREAMS;
+    const char *d = __builtin_strlen(e) == BR_CLASSES ? e : "023456";
     for (int c = 0; c < BR_CLASSES; c++) {
       const int v = d[c] - '0';
-      map[c] = (v < 0 || v >= SBX_AUX_STREAMS || v == 1) ? 0 : v;
+      s[c] = (v < 0 || v >= SBX_AUX_STREAMS || v == 1) ? 0 : v;
     }
   }
-  return map[cls];
-}
+};
+constexpr ClassStreams CLASS_STREAMS;
 
-static int rq_waves_per_cu() {
-  static const int f = sbx_env_tuning("SBX_PERMUTE_ROW_WAVES") ? atoi(sbx_env_tuning("SBX_PERMUTE_ROW_WAVES")) : 16;
-  return f < 1 ? 1 : f;
-}
+#ifndef SBX_PERMUTE_ROW_WAVES
+#define SBX_PERMUTE_ROW_WAVES 16
+#endif
+constexpr int RQ_WAVES_PER_CU = SBX_PERMUTE_ROW_WAVES < 1 ? 1 : SBX_PERMUTE_ROW_WAVES;
 
-static int tile_grid_factor() {  // SBX_PERMUTE_TILE_GRID: persistent tile waves per resident slot (tuning)
-  static const int f = sbx_env_tuning("SBX_PERMUTE_TILE_GRID") ? atoi(sbx_env_tuning("SBX_PERMUTE_TILE_GRID")) : 12;
-  return f < 1 ? 1 : f;
-}
+#ifndef SBX_PERMUTE_TILE_GRID
+#define SBX_PERMUTE_TILE_GRID 12  // persistent tile waves per resident slot
+#endif
+constexpr int64_t TILE_GRID_FACTOR = SBX_PERMUTE_TILE_GRID < 1 ? 1 : SBX_PERMUTE_TILE_GRID;
 
 #include "sbx_rowsort.h"
 
@@ -2539,7 +2547,7 @@ int block_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char
   // 0, 2, 3, ... (1 belongs to the long rows) and the radix kernel behind them joins them again on stream 0
   hipStream_t base = h->stream;
   const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
-  const int force = permute_force_radix() & 0xFF;
+  const int force = sbx_sw().permute_force_radix;
   size_t n_all = 0;
   for (int c = 0; c < BR_CLASSES; c++) n_all += n_block[c];
   unsigned *fb_rows = nullptr;  // rows whose columns cluster (listed by the class kernels, sorted by the radix kernel)
@@ -2550,9 +2558,9 @@ int block_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char
     /* resident workgroups per CU: LDS (12 B per slot) and ~24 waves (the kernels need 64..100 VGPRs) */          \
     const unsigned by_lds = (unsigned)(160 * 1024 / (br_cap(CLS) * 12 + 256)), by_waves = 24u / ((THREADS) / 64); \
     const unsigned per_cu = by_lds < by_waves ? by_lds : by_waves;                                                \
-    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * (unsigned)permute_grid_factor();           \
+    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * PERMUTE_GRID_FACTOR;                       \
     if (grid > n_block[CLS]) grid = n_block[CLS];                                                                 \
-    const int si = class_stream(CLS);                                                                             \
+    const int si = CLASS_STREAMS.s[CLS];                                                                          \
     if (fork && si) {                                                                                             \
       h->stream = h->aux_stream[si];                                                                              \
       SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[0], 0));                                              \
@@ -2578,18 +2586,19 @@ int block_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char
   if (n_block[CLS]) {                                                                                             \
     static_assert(4 * (THREADS) * (QUADS) == br_cap(CLS), "class capacity");                                      \
     const unsigned by_lds = (unsigned)(160 * 1024 / RqLds<VB, THREADS, QUADS>::BYTES);                            \
-    const unsigned by_waves = (unsigned)((THREADS) >= 512 ? 16 : rq_waves_per_cu()) / ((THREADS) / 64);           \
+    const unsigned by_waves = (unsigned)((THREADS) >= 512 ? 16 : RQ_WAVES_PER_CU) / ((THREADS) / 64);             \
     const unsigned per_cu = by_lds < by_waves ? by_lds : by_waves;                                                \
-    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * (unsigned)permute_grid_factor();           \
+    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * PERMUTE_GRID_FACTOR;                       \
     if (grid > n_block[CLS]) grid = n_block[CLS];                                                                 \
-    const int si = class_stream(CLS);                                                                             \
+    const int si = CLASS_STREAMS.s[CLS];                                                                          \
     if (fork && si) {                                                                                             \
       h->stream = h->aux_stream[si];                                                                              \
       SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[0], 0));                                              \
     }                                                                                                             \
     SBX_KLAUNCH(h, SBX_K_PERMUTE_BLOCK, (k_rows_quad<I, VB, THREADS, QUADS, MINW>), dim3(grid), dim3(THREADS), rec, \
                 col_in, val_in, col_order, rpo, block_rows + (CLS)*block_stride, (int)n_block[CLS], col_out,      \
-                val_out, st, force, fb_rows, &st->n_fb_rows, (const unsigned *)nullptr, table_bytes);             \
+                val_out, st, force | PERMUTE_ABLATE, fb_rows, &st->n_fb_rows, (const unsigned *)nullptr,           \
+                table_bytes);                                                                                     \
     if (fork && si) {                                                                                             \
       const hipError_t e1_ = hipEventRecord(h->aux_event[1 + si], h->stream);                                     \
       const hipError_t e2_ = hipStreamWaitEvent(base, h->aux_event[1 + si], 0);                                   \
@@ -2671,7 +2680,7 @@ template <typename I, int VB>
 int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char *val_in, const I *col_order,
                    const I *rpo, I *col_out, char *val_out, int64_t m, const I *long_rows,
                    unsigned n_long, int64_t long_nnz, PermState *st) {
-  if (!col_order || (permute_force_radix() & 1) || long_nnz >= ((int64_t)1 << 31))
+  if (!col_order || sbx_sw().permute_force_radix || long_nnz >= ((int64_t)1 << 31))
     return long_rows_radix_path<I, VB>(h, rec, col_in, val_in, col_order, rpo, col_out, val_out, m, long_rows, n_long,
                                     long_nnz, st);
   const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
@@ -2720,16 +2729,15 @@ int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char 
               long_nnz, target, (const unsigned *)rowmm, (const unsigned *)fine, (const unsigned *)segstart, cursor,
               (const unsigned *)row_skip, c2, v2);
   // the segments: virtual rows of the one-workgroup-per-row kernel (columns already relabelled: no column map)
-  const int force = permute_force_radix() & 0xFE;
   {
     // (512 threads, two workgroups per CU for segments of up to 4096 entries; 1024 threads for the longer ones)
     SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 512, 2, (VB == 8 ? 2 : 4)>), dim3(2 * (unsigned)h->num_cus), dim3(512),
                 (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo, (const I *)vlist,
-                0, col_out, val_out, st, force, fb_rows, &st->n_seg_fb_rows, (const unsigned *)&st->n_seg[0], 0u);
+                0, col_out, val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows, (const unsigned *)&st->n_seg[0], 0u);
     if constexpr (VB != 8) {
       SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 1024, 2, 1>), dim3((unsigned)h->num_cus), dim3(1024),
                   (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo,
-                  (const I *)(vlist + seg_max), 0, col_out, val_out, st, force, fb_rows, &st->n_seg_fb_rows,
+                  (const I *)(vlist + seg_max), 0, col_out, val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows,
                   (const unsigned *)&st->n_seg[1], 0u);
     }
   }
@@ -2740,7 +2748,7 @@ int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char 
   SBX_PROF_BYTES(h, SBX_K_PERMUTE_LONG, long_nnz * (int64_t)(2 * (sizeof(I) + VB)));
   PermState hs2;
   SBX_TRY(sbx_readback(h, &hs2, st, sizeof(PermState)));
-  if (sbx_env_tuning("SBX_DEBUG_LONG"))
+  if (SBX_DEBUG_LONG)
     fprintf(stderr, "long rows %u (%lld entries): segments %u + %u, clustered segments %u, rows left to the radix sort %u (%llu entries)\n",
             n_long, (long long)long_nnz, hs2.n_seg[0], hs2.n_seg[1], hs2.n_seg_fb_rows, hs2.n_long_fb, hs2.long_fb_nnz);
   if (hs2.n_long_fb)
@@ -2866,7 +2874,7 @@ int sort_stage(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *col_
   // profiler is on they run back to back, so that a kernel's event time is its own.
   bool has_block = false;
   for (int c = 0; c < BR_CLASSES; c++) has_block |= n_block[c] != 0;
-  const bool fork = !h->prof_on && permute_overlap() && total > 0 && (has_block || n_long);
+  const bool fork = !h->prof_on && sbx_sw().permute_overlap && total > 0 && (has_block || n_long);
   (void)total;
   hipStream_t main_stream = h->stream;
   if (fork) {
@@ -2891,10 +2899,10 @@ int sort_stage(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *col_
     const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
     // persistent waves, 15 per CU (the LDS of a tile) times 12 (measured: 1 ... 2 per slot lose 10 % to imbalance — a
     // tile is 30 ... 512 entries —, 8 ... 16 are level, one wave per tile is 7 % slower): each walks its tiles as a pipeline
-    const int64_t tile_grid = (int64_t)h->num_cus * 15 * tile_grid_factor();
+    const int64_t tile_grid = (int64_t)h->num_cus * 15 * TILE_GRID_FACTOR;
     // the relabelling permutes whose arrays fit 32-bit byte offsets and whose ids fit the map's words: k_permute_tile2
     constexpr uint64_t EB = sizeof(I) > (size_t)VB ? sizeof(I) : (size_t)VB;
-    const bool tile2 = cdf && cdf->table && col_order && permute_force_radix() == 0 && nnz_in < ((int64_t)1 << 28) &&
+    const bool tile2 = cdf && cdf->table && col_order && !sbx_sw().permute_force_radix && !PERMUTE_ABLATING && nnz_in < ((int64_t)1 << 28) &&
                        (uint64_t)nnz_in * EB <= PT2_MAX_BYTES && (uint64_t)total * EB <= PT2_MAX_BYTES &&
                        (uint64_t)m * sizeof(I) <= PT2_MAX_BYTES;
     if (tile2) {
@@ -2906,14 +2914,14 @@ int sort_stage(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *col_
     } else {
     SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile<I, VB>), dim3((unsigned)(tiles < tile_grid ? tiles : tile_grid)),
                 dim3(PT_THREADS), rec, col_in, val_in, col_order, rpo, sp, (const I *)tile_first, col_out, val_out, nr,
-                st, col_bits, permute_force_radix(), fb_tiles, (int64_t)tiles);
+                st, col_bits, (int)sbx_sw().permute_force_radix, fb_tiles, (int64_t)tiles);
     SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile_radix<I, VB>), dim3((unsigned)(tiles < 2048 ? tiles : 2048)),
                 dim3(PT_THREADS), rec, col_in, val_in, col_order, rpo, sp, (const I *)tile_first, col_out, val_out, nr,
                 st, col_bits, (const unsigned *)fb_tiles);
     }
     SBX_LAUNCH_CHECK(h);
     SBX_PROF_BYTES(h, SBX_K_PERMUTE_TILE, short_nnz * (int64_t)(2 * (sizeof(I) + VB)));
-    if ((permute_force_radix() >> 8) == 9) {  // diagnostic: print and clear the phase stamps
+    if constexpr (TILE_STOP == 9) {  // diagnostic: print and clear the phase stamps
       unsigned long long hs_[32];
       SBX_HIP(h, hipStreamSynchronize(h->stream));
       SBX_HIP(h, hipMemcpyFromSymbol(hs_, HIP_SYMBOL(g_tile_stamps), sizeof(hs_)));
@@ -3094,9 +3102,8 @@ static int permute_csr_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, 
   CdfMap cdf;
   cdf.table = nullptr, cdf.shift = 0, cdf.fsh = 0;
   bool cdf_on_side = false;
-  static const bool tile2_off = sbx_env_test("SBX_PERMUTE_NO_TILE2") != nullptr;  // (tests: the equal-width tile kernel)
-  if (col_order && nnz > 0 && !tile2_off) {
-    if (!h->prof_on && permute_overlap() && sbx_aux_streams(h) == SBX_OK) {
+  if (col_order && nnz > 0 && !sbx_sw().permute_no_tile2) {
+    if (!h->prof_on && sbx_sw().permute_overlap && sbx_aux_streams(h) == SBX_OK) {
       hipStream_t main_stream = h->stream;
       SBX_HIP(h, hipEventRecord(h->aux_event[0], main_stream));
       SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[0], 0));

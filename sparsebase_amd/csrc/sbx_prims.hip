@@ -562,10 +562,10 @@ __global__ __launch_bounds__(RSP_THREADS, 4) void k_onesweep_pass(const K *__res
 #undef RS_COUNT_PUBLISH
 }
 
-static int rs_hist_grid_factor() {  // SBX_RADIX_HIST_GRID: workgroups per CU of the histogram kernel (tuning)
-  static const int f = sbx_env_tuning("SBX_RADIX_HIST_GRID") ? atoi(sbx_env_tuning("SBX_RADIX_HIST_GRID")) : 2;
-  return f < 1 ? 1 : f;
-}
+#ifndef SBX_RADIX_HIST_GRID
+#define SBX_RADIX_HIST_GRID 2  // workgroups per CU of the histogram kernel
+#endif
+constexpr int RS_HIST_GRID_FACTOR = SBX_RADIX_HIST_GRID < 1 ? 1 : SBX_RADIX_HIST_GRID;
 
 template <typename K, typename P, int ITEMS, bool HAS_P, bool EMIT = false>
 static int radix_sort_impl(sbx_handle_t h, K *ka, K *kb, P *va, P *vb, int64_t count, const sbx_radix_pass *passes,
@@ -596,7 +596,7 @@ static int radix_sort_impl(sbx_handle_t h, K *ka, K *kb, P *va, P *vb, int64_t c
   // few, fat workgroups: every workgroup ends with passes x 256 adds on the same histogram words, and one word takes
   // only ~88 adds per microsecond whoever issues them
   SBX_KLAUNCH(h, SBX_K_RADIX_HIST, (k_onesweep_hist<K>),
-              dim3(sbx_grid_for(count, RSH_THREADS * 16, (int64_t)h->num_cus * rs_hist_grid_factor())), dim3(RSH_THREADS),
+              dim3(sbx_grid_for(count, RSH_THREADS * 16, (int64_t)h->num_cus * RS_HIST_GRID_FACTOR)), dim3(RSH_THREADS),
               (const K *)ka, count, plan, ghist, state, state_words);
   SBX_PROF_BYTES(h, SBX_K_RADIX_HIST, count * (int64_t)sizeof(K));  // one read of the keys for all passes
   K *src_k = ka, *dst_k = kb;
@@ -652,7 +652,7 @@ static int radix_sort_io_impl(sbx_handle_t h, const sbx_radix_side *src, K *ka, 
   rs_word *state = nullptr;
   SBX_TRY(sbx_salloc(h, state_words, &state));
   SBX_KLAUNCH(h, SBX_K_RADIX_HIST, (k_onesweep_hist<K, KSPLIT>),
-              dim3(sbx_grid_for(count, RSH_THREADS * 16, (int64_t)h->num_cus * rs_hist_grid_factor())), dim3(RSH_THREADS),
+              dim3(sbx_grid_for(count, RSH_THREADS * 16, (int64_t)h->num_cus * RS_HIST_GRID_FACTOR)), dim3(RSH_THREADS),
               (const K *)src->k[0], count, plan, ghist, state, state_words, (const uint32_t *)src->k[1]);
   SBX_PROF_BYTES(h, SBX_K_RADIX_HIST, count * (int64_t)sizeof(K));
   constexpr size_t lds_bytes = sizeof(K) * TILE + (HAS_P ? sizeof(P) * TILE : 0) + (RSP_WAVES + 2) * 256 * 4 + 64;

@@ -607,39 +607,14 @@ __global__ __launch_bounds__(256) void k_bfs_start(const X *__restrict__ rp, uns
 // append must not cost one atomic per ballot.
 constexpr int RCM_STAGE = 512;  // staged vertices per wave
 
-// bottom-up is chosen when the frontier owns more than this many times the edges of the unvisited rest
-static double bu_ratio() {
-  static const double r = sbx_env_test("SBX_DEBUG_BU_RATIO") ? atof(sbx_env_test("SBX_DEBUG_BU_RATIO")) : 4.0;
-  return r;
-}
-
-// calls a handle keeps away from the persistent kernels after a grid barrier gave up (SBX_DEBUG_GB_BACKOFF: stress tests
-// set 0 so that every call tries them again)
-static int gb_backoff_calls() {
-  static const int k = sbx_env_test("SBX_DEBUG_GB_BACKOFF") ? atoi(sbx_env_test("SBX_DEBUG_GB_BACKOFF")) : 16;
-  return k;
-}
-
-static bool rcm_split_expand() {  // SBX_RCM_SPLIT_EXPAND=0: a wide frontier's light rows are expanded in front of its hubs
-  static const bool on = !(sbx_env_test("SBX_RCM_SPLIT_EXPAND") && atoi(sbx_env_test("SBX_RCM_SPLIT_EXPAND")) == 0);
-  return on;
-}
-
-static bool rcm_cc_overlap() {  // SBX_RCM_CC_OVERLAP=0: the labelling of the other components runs in line (see sbx_rcm_reorder)
-  static const bool on = !(sbx_env_test("SBX_RCM_CC_OVERLAP") && atoi(sbx_env_test("SBX_RCM_CC_OVERLAP")) == 0);
-  return on;
-}
-
-static bool rcm_overlap() {
-  static const bool on = !(sbx_env_test("SBX_RCM_OVERLAP") && atoi(sbx_env_test("SBX_RCM_OVERLAP")) == 0);
-  return on;
-}
-
 // first candidate root of the pseudo-peripheral search whose Cuthill-McKee sweep is run speculatively
-static int64_t rcm_speculate_from() {
-  static const int64_t k = sbx_env_tuning("SBX_DEBUG_RCM_SPECULATE") ? atoll(sbx_env_tuning("SBX_DEBUG_RCM_SPECULATE")) : 2;
-  return k;
-}
+#ifndef SBX_DEBUG_RCM_SPECULATE
+#define SBX_DEBUG_RCM_SPECULATE 2
+#endif
+constexpr int64_t RCM_SPECULATE_FROM = SBX_DEBUG_RCM_SPECULATE;
+#ifndef SBX_DEBUG_RCM_LEVELS
+#define SBX_DEBUG_RCM_LEVELS 0  // 1: the ordered sweeps print every level (diagnostic variant builds)
+#endif
 
 struct WaveStage {
   I *buf;                  // this wave's LDS slice
@@ -1971,23 +1946,7 @@ __global__ __launch_bounds__(256) void k_write_component(const I *__restrict__ q
   for (; j < cnt; j += stride) inv[q[j]] = base + (I)(cnt - 1 - j);
 }
 
-// SBX_RCM_COUNT_SORT=0: levels above 4096 vertices are ordered by the generic radix sort over (parent position, low field)
-static bool rcm_count_sort() {
-  static const bool on = !(sbx_env_test("SBX_RCM_COUNT_SORT") && atoi(sbx_env_test("SBX_RCM_COUNT_SORT")) == 0);
-  return on;
-}
-
 constexpr int64_t RCM_COUNT_SORT_MAX = (int64_t)1 << 20;  // levels above this: the generic sort's staged stores win
-
-static bool rcm_ranked_keys() {  // SBX_RCM_RANKED_KEYS=0: big Cuthill-McKee levels sort their full (parent position, rank) keys
-  static const bool on = !(sbx_env_test("SBX_RCM_RANKED_KEYS") && atoi(sbx_env_test("SBX_RCM_RANKED_KEYS")) == 0);
-  return on;
-}
-
-static int rcm_ranked_div() {  // ... for levels of at least n_ranked / this many vertices (SBX_DEBUG_RCM_RANKED_DIV)
-  static const int v = sbx_env_test("SBX_DEBUG_RCM_RANKED_DIV") ? atoi(sbx_env_test("SBX_DEBUG_RCM_RANKED_DIV")) : 3;
-  return v > 0 ? v : 1;
-}
 
 struct BfsBuffers {
   bool *claim_clean;  // the claim bytes of the unordered sweeps are all zero (a finished sweep leaves them that way)
@@ -2123,7 +2082,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
     try_small = true;
     if (!expanded_by_small) {
     // (frontier_unmarked is consumed by the expansion right below)
-    const bool bottom_up = frontier_edges >= 0 && fsize >= 8192 && (double)frontier_edges > bu_ratio() * (double)remaining;
+    const bool bottom_up = frontier_edges >= 0 && fsize >= 8192 && (double)frontier_edges > sbx_sw().bu_ratio * (double)remaining;
     if (bottom_up) {
       if (frontier_unmarked) {
         SBX_HIP(h, hipMemsetAsync(b.fbits, 0, bm_bytes, h->stream));
@@ -2147,7 +2106,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
       // idle — used to run in front of the hub kernel because it also queues the hubs' chunks.  Now a first launch only
       // queues (part 1: ~10 us), the hub kernel follows at once and the light rows (part 2) run beside it on a side
       // stream: 85 us off the widest level of the bench matrix's Cuthill-McKee sweep.
-      const bool split = b.max_deg > (unsigned)RCM_LIGHT && fsize >= 4096 && !h->prof_on && rcm_split_expand() && h->aux_ready;
+      const bool split = b.max_deg > (unsigned)RCM_LIGHT && fsize >= 4096 && !h->prof_on && sbx_sw().rcm_split_expand && h->aux_ready;
       if (split) {
         hipStream_t main_s = h->stream;
         const bool was_dirty = h->aux_dirty;
@@ -2183,8 +2142,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
     }
     frontier_unmarked = false;
     const unsigned nf = hd.nf;
-    static const bool trace_levels = sbx_env_tuning("SBX_DEBUG_RCM_LEVELS") && atoi(sbx_env_tuning("SBX_DEBUG_RCM_LEVELS")) != 0;
-    if (trace_levels)
+    if (SBX_DEBUG_RCM_LEVELS)
       fprintf(stderr, "[rcm %s] level %u: frontier %u vertices / %lld edges, unvisited edges %lld -> %u new vertices / %llu edges\n",
               CM ? "cm" : "plain", level, fsize, (long long)frontier_edges, (long long)remaining, nf,
               (unsigned long long)hd.fedges);
@@ -2196,7 +2154,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
     I *q_next = b.q + off + fsize;
     // direction of the NEXT expansion is already decidable: the frontier marks (bitmap +
     // level positions) are only written when it will be bottom-up
-    const bool next_bottom_up = nf >= 8192 && (double)frontier_edges > bu_ratio() * (double)remaining;
+    const bool next_bottom_up = nf >= 8192 && (double)frontier_edges > sbx_sw().bu_ratio * (double)remaining;
     const int mark_frontier = next_bottom_up ? 1 : 0;
     // levels wide enough for the bitmap pass (k_fresh_words / k_visited_from_ppos) get every word of fbits rewritten
     const bool bitmap_pass = nf > (unsigned)RCM_LDS_SORT && (int64_t)nf >= std::max<int64_t>(RCM_REBUILD_BITS, b.n / 128);
@@ -2211,7 +2169,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
       sbx_radix_pass passes[16];
       int np;
       int low_bits = 32;  // width of the key's low field (vertex id or degree rank); 32: the parent position starts at bit 32
-      if (rcm_count_sort() && (int64_t)nf <= RCM_COUNT_SORT_MAX) {
+      if (sbx_sw().rcm_count_sort && (int64_t)nf <= RCM_COUNT_SORT_MAX) {
         // The level's vertices in the order of their low key field — ascending degree rank (Cuthill-McKee) or id
         // (plain) — read off a bitmap, so that only the parent positions are left to sort, stably, by the counting
         // sort of sbx_countsort.h: three small launches per 9-bit digit.  The bitmap comes from a pass over all
@@ -2259,7 +2217,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
                     (const unsigned *)b.ppos, (const uint32_t *)nullptr, b.ka, (uint32_t *)nullptr, (uint32_t *)nullptr, words,
                     b.dv);
         np = sbx_radix_plan(0, 0, 32, 32 + sbx_bits_for((uint64_t)(fsize - 1)), passes);
-      } else if (CM && !set_bits && rcm_ranked_keys() && (int64_t)nf * rcm_ranked_div() >= b.n_ranked) {
+      } else if (CM && !set_bits && sbx_sw().rcm_ranked_keys && (int64_t)nf * sbx_sw().rcm_ranked_div >= b.n_ranked) {
         // keys in ascending degree-rank order from a bitmap in rank space: only the parent positions are left to sort
         const int64_t words = (b.n_ranked + 63) / 64;
         const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
@@ -2322,17 +2280,14 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
 // -> w_L downwards (k_ubfs_descend_step) costs a few adjacency scans where the ordered sweep sorted every level.
 // Deep, narrow graphs (a sweep of more than 64 levels) keep the ordered sweep, whose small levels run in one
 // persistent workgroup.
-static unsigned ub_max_levels() {  // SBX_DEBUG_UB_MAX_LEVELS: deeper sweeps fall back to the ordered kind (tests raise it)
-  static const unsigned v = sbx_env_test("SBX_DEBUG_UB_MAX_LEVELS") ? (unsigned)atoll(sbx_env_test("SBX_DEBUG_UB_MAX_LEVELS")) : 64u;
-  return v;
-}
+// (sbx_switches::ub_max_levels: SBX_DEBUG_UB_MAX_LEVELS, tests raise it)
 
 // an unordered bottom-up step stops at a vertex's first frontier neighbour, so it pays off much earlier than the ordered
 // one, which must see every neighbour: bottom-up when the frontier owns more than this many times the unvisited edges
-static double ubu_ratio() {
-  static const double r = sbx_env_tuning("SBX_DEBUG_UBU_RATIO") ? atof(sbx_env_tuning("SBX_DEBUG_UBU_RATIO")) : 0.5;
-  return r;
-}
+#ifndef SBX_DEBUG_UBU_RATIO
+#define SBX_DEBUG_UBU_RATIO 0.5
+#endif
+constexpr double UBU_RATIO = SBX_DEBUG_UBU_RATIO;
 
 #ifndef SBX_UR_GRID
 #define SBX_UR_GRID 64  // (128: +1 %, 256: +4 % on the bench matrix's RCM, measured again in round 6 with tools/build_variant.py)
@@ -2378,19 +2333,10 @@ __device__ __forceinline__ void uc_begin(RcmDev *dv, const ChainInit &ci) {
   dv->uc_flips = 0;
   dv->uc_small_ran = 0;
 }
-// levels an unordered sweep enqueues behind a big one without waiting for it (run_ubfs); SBX_RCM_UBFS_CHAIN=0: none
-static int ubfs_chain() {
-  // (3: a sweep of the bench matrix has three bottom-up levels in a row — behind a bottom-up level of the host's the
-  // last link finds nothing to do, 5 us; behind a top-down level all three run.  With 2 the second sweep needs another
-  // round trip and leaves two links idle)
-  static const int k = sbx_env_test("SBX_RCM_UBFS_CHAIN") ? atoi(sbx_env_test("SBX_RCM_UBFS_CHAIN")) : 3;
-  return k < 0 ? 0 : (k > 8 ? 8 : k);
-}
-
-static bool rcm_unordered() {  // SBX_RCM_UNORDERED=0: every sweep of the search keeps the order inside its levels
-  static const bool on = !(sbx_env_test("SBX_RCM_UNORDERED") && atoi(sbx_env_test("SBX_RCM_UNORDERED")) == 0);
-  return on;
-}
+// levels an unordered sweep enqueues behind a big one without waiting for it (run_ubfs): sbx_switches::rcm_ubfs_chain
+// (3: a sweep of the bench matrix has three bottom-up levels in a row — behind a bottom-up level of the host's the last
+// link finds nothing to do, 5 us; behind a top-down level all three run.  With 2 the second sweep needs another round
+// trip and leaves two links idle)
 
 __global__ __launch_bounds__(256) void k_ubfs_start(const X *__restrict__ rp, unsigned *__restrict__ vbits,
                                                     unsigned *__restrict__ fbits, unsigned *__restrict__ dist,
@@ -2665,8 +2611,7 @@ constexpr unsigned UB_TIES_SMALL = 8192;
 // candidate under w_{k-1}: a pattern that is not symmetric) makes it LEAVE with nothing changed — the T_k live in the
 // scratch behind the candidates' list and in LDS, not in the cone bitmap — and the persistent kernels, which are enqueued
 // behind it either way and leave at once when it has named the root (dv->tie_done), take over.
-constexpr unsigned TS_CAP = 1024, TS_LEVELS = 64, TS_EDGES = 1u << 17, TS_HASH = 4096;
-constexpr unsigned TS_SINGLE = 1u << 13;  // entries of a smallest-member step the one workgroup still scans itself
+constexpr unsigned TS_LEVELS = 64, TS_HASH = 4096;  // (TS_CAP, TS_EDGES, TS_SINGLE: sbx_internal.h, next to the switches)
 constexpr unsigned TS_GATHER = 1u << 14;  // entries of an ordinary marking step (visited word + level gathered per entry)
 struct TieWalkState {  // between k_ubfs_ties_small, k_tie_heavy_min and k_tie_walk_resume (device memory)
   unsigned req;        // 1: the step k -> k - 1 is the grid's; anything else: nothing to resume
@@ -3031,23 +2976,6 @@ __global__ __launch_bounds__(256) void k_tie_heavy_min(const X *__restrict__ rp,
   if (threadIdx.x == 0 && m != 0xFFFFFFFFu) atomicMin(&st->min_id, m);
 }
 
-static bool rcm_tie_walk() {  // SBX_RCM_TIE_WALK=0: every tie-break through the persistent kernels (tests, A/B)
-  static const bool on = !(sbx_env_test("SBX_RCM_TIE_WALK") && atoi(sbx_env_test("SBX_RCM_TIE_WALK")) == 0);
-  return on;
-}
-// SBX_DEBUG_TIE_EDGES / SBX_DEBUG_TIE_CAP: the walk's limits, lowered (tests: small graphs then leave it at every exit)
-static unsigned tie_walk_edges() {
-  static const unsigned v = sbx_env_test("SBX_DEBUG_TIE_EDGES") ? (unsigned)atoll(sbx_env_test("SBX_DEBUG_TIE_EDGES")) : TS_EDGES;
-  return v < TS_EDGES ? v : TS_EDGES;
-}
-static unsigned tie_walk_single() {  // SBX_DEBUG_TIE_SINGLE: entries above which a smallest-member step goes to the grid
-  static const unsigned v = sbx_env_test("SBX_DEBUG_TIE_SINGLE") ? (unsigned)atoll(sbx_env_test("SBX_DEBUG_TIE_SINGLE")) : TS_SINGLE;
-  return v < TS_SINGLE ? v : TS_SINGLE;
-}
-static unsigned tie_walk_cap() {
-  static const unsigned v = sbx_env_test("SBX_DEBUG_TIE_CAP") ? (unsigned)atoll(sbx_env_test("SBX_DEBUG_TIE_CAP")) : TS_CAP;
-  return v < TS_CAP ? v : TS_CAP;
-}
 
 // ... and, behind it, the walk's step at the same level: the smallest member of T_k adjacent to w_{k-1} = st->min_id (the
 // members' entries again — consecutive ones, coalesced — compared with one vertex: no gathers)
@@ -3241,7 +3169,7 @@ constexpr unsigned UB_DESC_GRID = 64;
 // milliseconds; a barrier normally takes a microsecond or two) the waiter raises dv->gb_abort and leaves, every other
 // waiter sees the flag and leaves too, late workgroups leave at their first barrier, and the host — which finds the flag
 // in its next read-back — throws the sweep away and runs it again with the one-launch-per-level kernels.
-constexpr unsigned GB_SPINS = 1u << 16;
+// (GB_SPINS: sbx_internal.h, the default of SBX_DEBUG_GB_SPINS)
 // THE INVARIANT the barriers rest on: every word one workgroup hands to another between two barriers is written and
 // read with agent-scope atomics (relaxed: they go past the per-XCD L2s, the barrier orders them), and a wave drains its
 // vector-memory counter (vmcnt 0) before its workgroup's arrival is counted.  There is no release / acquire fence in
@@ -3762,9 +3690,8 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
                          (unsigned *)claim8, *b.claim_clean ? 0ull : (unsigned long long)((b.n + 3) / 4)};
   *b.claim_clean = false;  // (until this sweep has run to its end: every level's collection pass clears what it read)
   unsigned *dist = b.lpos;  // level positions are an ordered sweep's business: the array is free here
-  static const unsigned gb_spins = sbx_env_test("SBX_DEBUG_GB_SPINS") ? (unsigned)atoll(sbx_env_test("SBX_DEBUG_GB_SPINS")) : GB_SPINS;
   SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_start, dim3(RCM_START_GRID), dim3(256), b.rp, b.vbits, b.fbits, dist, b.q, b.dv,
-              fixed_root, gb_spins, sc);
+              fixed_root, sbx_sw().gb_spins, sc);
   unsigned off = 0, fsize = 1, level = 0, total = 1;
   const unsigned max_grid = (unsigned)h->num_cus * 8;
   static int heavy_per_cu = 0;
@@ -3778,7 +3705,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
   unsigned *cur_f = b.fbits, *cur_n = nbits_buf;  // frontier bitmap / the one a bottom-up level writes (swapped after it)
   bool fbits_valid = true;  // cur_f holds exactly the current frontier (the root, or what the level kernels left)
   unsigned rounds = 0;      // host round trips of this sweep
-  static const bool dbg_check = sbx_env_test("SBX_DEBUG_RCM_CHECK") && atoi(sbx_env_test("SBX_DEBUG_RCM_CHECK")) != 0;
+  const bool dbg_check = sbx_sw().rcm_check;
   std::vector<std::string> trace;
   auto note = [&](const char *what, unsigned a, unsigned b_, long long c) {
     if (!dbg_check) return;
@@ -3788,24 +3715,23 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
     trace.push_back(buf);
   };
   while (true) {
-    if (++rounds > ub_max_levels()) {
+    if (++rounds > sbx_sw().ub_max_levels) {
       *too_deep = true;
       return SBX_OK;
     }
     if (frontier_edges < 0 || (frontier_edges <= (int64_t)UR_MAX_E && fsize <= UR_MAX_N)) {
       // small levels: as many as stay small, in one launch
       SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                  (I *)b.heavy, b.dv, off, fsize, level, total, (long long)frontier_edges, ub_max_levels(), 0);
+                  (I *)b.heavy, b.dv, off, fsize, level, total, (long long)frontier_edges, sbx_sw().ub_max_levels, 0);
       // At a sweep's start on a big graph this run usually ends at a frontier for the bottom-up kernels: the chain that
       // follows is enqueued now and begun on the device (k_ubfs_chain_from_small) — one read-back for the head run and the
       // chain instead of two.  Where the run ends otherwise (the sweep is over, a top-down level is due, too deep) the
       // half-dozen launches leave at once: only where it can pay (BfsBuffers::head_chain, a graph that is not small).
-      static const bool head_chain_on = !(sbx_env_test("SBX_RCM_HEAD_CHAIN") && atoi(sbx_env_test("SBX_RCM_HEAD_CHAIN")) == 0);
       const int spec_len =
-          (head_chain_on && b.head_chain && frontier_edges < 0 && b.n >= ((int64_t)1 << 17)) ? ubfs_chain() : 0;
+          (sbx_sw().rcm_head_chain && b.head_chain && frontier_edges < 0 && b.n >= ((int64_t)1 << 17)) ? sbx_sw().rcm_ubfs_chain : 0;
       if (spec_len > 0) {
-        const ChainInit ci0 = {0u, 0u, 0u, 0u, 0ll, ubu_ratio()};
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_from_small, dim3(1), dim3(1), b.dv, (long long)remaining, ubu_ratio(),
+        const ChainInit ci0 = {0u, 0u, 0u, 0u, 0ll, UBU_RATIO};
+        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_from_small, dim3(1), dim3(1), b.dv, (long long)remaining, UBU_RATIO,
                     level);
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
                     (const unsigned *)b.vbits, (const unsigned *)dist, 0u, b.n, cur_f, (const RcmDev *)b.dv);
@@ -3815,9 +3741,8 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
                       b.vbits, (const unsigned *)cf, cn, dist, 0u, b.q, b.n, b.dv, 1, ci0);
           std::swap(cf, cn);
         }
-        static const int tail_mode0 = sbx_env_test("SBX_DEBUG_CHAIN_TAIL_ABORT") && atoi(sbx_env_test("SBX_DEBUG_CHAIN_TAIL_ABORT")) ? 2 : 1;
         SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                    (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, ub_max_levels(), tail_mode0);
+                    (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
       }
       SBX_LAUNCH_CHECK(h);
       // (the hook's work needs the degree counts: while this read-back is the one that delivers them it waits for the
@@ -3840,7 +3765,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
       }
       if (hs.gb_abort) {  // a grid barrier gave up (gb_wait): this sweep is redone by the ordered kernels
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-        h->rcm_gb_backoff = gb_backoff_calls();
+        h->rcm_gb_backoff = sbx_sw().gb_backoff;
         *too_deep = true;
         return SBX_OK;
       }
@@ -3885,10 +3810,10 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
     }
     I *q_next = b.q + off + fsize;  // the next level is appended to the queue
     const UnorderedSweep us = {claim8, nullptr, dist, level + 1};
-    const bool bottom_up = frontier_edges >= 0 && fsize >= 1024 && (double)frontier_edges > ubu_ratio() * (double)remaining;
+    const bool bottom_up = frontier_edges >= 0 && fsize >= 1024 && (double)frontier_edges > UBU_RATIO * (double)remaining;
     note(bottom_up ? "bottom-up" : "top-down", fbits_valid, 0, 0);
-    const int chain_len = ubfs_chain();
-    const ChainInit ci = {off, fsize, level, total, (long long)remaining, ubu_ratio()};
+    const int chain_len = sbx_sw().rcm_ubfs_chain;
+    const ChainInit ci = {off, fsize, level, total, (long long)remaining, UBU_RATIO};
     if (bottom_up) {
       if (!fbits_valid)
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
@@ -3916,7 +3841,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
     fbits_valid = true;
     RcmDev hd;
     if (chain_len > 0) {
-      // The levels behind this one are enqueued without waiting for it: up to ubfs_chain() bottom-up levels and the
+      // The levels behind this one are enqueued without waiting for it: up to sbx_sw().rcm_ubfs_chain bottom-up levels and the
       // persistent small-level kernel.  Each runs only if the state the level in front of it left says so — its last
       // workgroup out applies the rules of this loop on the device (uc_advance) — and ONE read-back serves them all.
       // A sweep of the bench matrix: a small run, three bottom-up levels, a small run — five round trips, now two.
@@ -3926,9 +3851,8 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
                     b.vbits, (const unsigned *)cf, cn, dist, 0u, b.q, b.n, b.dv, 1, ci);
         std::swap(cf, cn);
       }
-      static const int tail_mode = sbx_env_test("SBX_DEBUG_CHAIN_TAIL_ABORT") && atoi(sbx_env_test("SBX_DEBUG_CHAIN_TAIL_ABORT")) ? 2 : 1;
       SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                  (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, ub_max_levels(), tail_mode);
+                  (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
       SBX_LAUNCH_CHECK(h);
       SBX_TRY(bfs_first_launch(b, 150));  // (a chain of big levels is in flight: the host has nothing else to do)
       SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
@@ -3936,7 +3860,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
         // a grid barrier of the chain's small-level kernel gave up — before it could say that it ran at all: the sweep
         // is redone by the ordered kernels, as after the small-level kernel at the head of the loop
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-        h->rcm_gb_backoff = gb_backoff_calls();
+        h->rcm_gb_backoff = sbx_sw().gb_backoff;
         *too_deep = true;
         return SBX_OK;
       }
@@ -3998,10 +3922,6 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
 // the next candidate root after an unordered sweep: first vertex in queue order among the deepest level's vertices of
 // smallest degree (see the comment above k_ubfs_start); left in dv->root
 __global__ void k_clear_spec_guard(RcmDev *__restrict__ dv) { dv->spec_guard = 0; }
-static bool rcm_tie_spec() {  // SBX_RCM_TIE_SPEC=0: the host looks at every tie walk's outcome before it enqueues the next sweep
-  static const bool on = !(sbx_env_test("SBX_RCM_TIE_SPEC") && atoi(sbx_env_test("SBX_RCM_TIE_SPEC")) == 0);
-  return on;
-}
 static int ubfs_pick_root_slow(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, const BfsResult &r, bool *aborted,
                                bool clear_guard);
 // allow_unverified: the caller's next sweep can be redone (run_ubfs / run_bfs with spec_failed): a tie walk is then left
@@ -4017,17 +3937,17 @@ static int ubfs_pick_root(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, c
     // it leave at once unless it handed a step over to them)
     TieWalkState *tw = nullptr;
     SBX_TRY(sbx_salloc(h, 1, &tw));
-    static const bool tw_dbg = sbx_env_test("SBX_DEBUG_TIE_WALK") != nullptr;
-    const bool spec = allow_unverified && rcm_tie_walk() && rcm_tie_spec() && !tw_dbg && b.tie_unverified;
+    const bool tw_dbg = sbx_sw().tie_walk_debug;
+    const bool spec = allow_unverified && sbx_sw().rcm_tie_walk && sbx_sw().rcm_tie_spec && !tw_dbg && b.tie_unverified;
     SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_ties_small, dim3(1), dim3(1024), b.rp, last, r.last_size, cone, list, b.dv, b.col,
-                (const unsigned *)b.vbits, (const unsigned *)b.lpos, rcm_tie_walk() ? r.levels : 0u, tie_walk_edges(),
-                tie_walk_cap(), tie_walk_single(), tw, spec ? 1u : 0u);
-    if (rcm_tie_walk()) {
+                (const unsigned *)b.vbits, (const unsigned *)b.lpos, sbx_sw().rcm_tie_walk ? r.levels : 0u, sbx_sw().tie_edges,
+                sbx_sw().tie_cap, sbx_sw().tie_single, tw, spec ? 1u : 0u);
+    if (sbx_sw().rcm_tie_walk) {
       SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_min, dim3((unsigned)h->num_cus), dim3(256), b.rp, b.col,
                   (const unsigned *)b.vbits, (const unsigned *)b.lpos, (const I *)list, tw);
       SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_adj, dim3((unsigned)h->num_cus), dim3(256), b.rp, b.col, (const I *)list, tw);
       SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_walk_resume, dim3(1), dim3(1024), b.rp, b.col, (const unsigned *)b.vbits,
-                  (const unsigned *)b.lpos, list, b.dv, tw, tie_walk_edges(), tie_walk_cap(), tie_walk_single());
+                  (const unsigned *)b.lpos, list, b.dv, tw, sbx_sw().tie_edges, sbx_sw().tie_cap, sbx_sw().tie_single);
       // Usually that was the whole tie-break — so the next sweep goes out behind it unseen: its first kernels leave if the
       // walk did (RcmDev::spec_guard), its first read-back tells, and the caller then comes back for the persistent
       // kernels (ubfs_pick_root_slow).  One round trip per tie-break saved.
@@ -4101,7 +4021,7 @@ static int ubfs_pick_root_slow(sbx_handle_t h, const BfsBuffers &b, unsigned *co
     SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
     if (hd.gb_abort) {
       SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-      h->rcm_gb_backoff = gb_backoff_calls();
+      h->rcm_gb_backoff = sbx_sw().gb_backoff;
       *aborted = true;
       return SBX_OK;
     }
@@ -4124,7 +4044,7 @@ static int ubfs_pick_root_slow(sbx_handle_t h, const BfsBuffers &b, unsigned *co
   SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
   if (hd.gb_abort) {
     SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-    h->rcm_gb_backoff = gb_backoff_calls();
+    h->rcm_gb_backoff = sbx_sw().gb_backoff;
     *aborted = true;
   }
   return SBX_OK;
@@ -4214,13 +4134,13 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   SBX_LAUNCH_CHECK(h);
   // after a grid barrier gave up (a GPU shared with another process, see gb_wait) the next few calls on this handle do
   // not try the persistent kernels again
-  const bool unordered_ok = rcm_unordered() && h->rcm_gb_backoff == 0;
+  const bool unordered_ok = sbx_sw().rcm_unordered && h->rcm_gb_backoff == 0;
   if (h->rcm_gb_backoff > 0) h->rcm_gb_backoff--;
   // The degree counts (non-empty rows, largest degree, first non-empty vertex) are read back with the first sweep's first
   // round trip when that sweep is an unordered one: it starts from dv->root, which k_deg_reduce set, and needs nothing
   // else the host does not know yet.  (~17 us per call: a read-back kernel and a launch gap.)
   // (only with the side stream: without one the degree ranks are enqueued before the first sweep and need the counts)
-  const bool lazy_counts = unordered_ok && !h->prof_on && rcm_overlap();
+  const bool lazy_counts = unordered_ok && !h->prof_on && sbx_sw().rcm_overlap;
   RcmDev hd0;
   bool hd0_ready = false;
   if (!lazy_counts) {
@@ -4232,7 +4152,7 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   // launch- and latency-bound — run on the caller's stream, and joined before the first Cuthill-McKee sweep.
   const uint32_t *dorder = nullptr;
   hipStream_t main_stream = h->stream;
-  const bool side = !h->prof_on && rcm_overlap();
+  const bool side = !h->prof_on && sbx_sw().rcm_overlap;
   BfsBuffers b;
   if (side) {  // (recorded here: the side stream waits for the counts above, not for the sweep enqueued before its work)
     SBX_TRY(sbx_aux_streams(h));
@@ -4385,7 +4305,7 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
           }
           return SBX_OK;
         };
-        if (candidate >= rcm_speculate_from()) {
+        if (candidate >= RCM_SPECULATE_FROM) {
           SBX_TRY(join_ranks());
           bool sf = false;
           SBX_TRY(run_bfs<true>(h, b, fixed, root, &r, &sf));
@@ -4478,7 +4398,7 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   // on the bench matrix — run on a side stream while the caller's stream goes on with that component's search and
   // Cuthill-McKee sweep, which are bound by launches and latency, not by bandwidth.  The search needs no labels (a sweep
   // cannot leave its component; unlabelled, the bottom-up levels merely look at the other components' vertices too).
-  cc_forked = side && v0 >= 0 && r0.count > (unsigned)RCM_MID && r0_unordered && rcm_cc_overlap();
+  cc_forked = side && v0 >= 0 && r0.count > (unsigned)RCM_MID && r0_unordered && sbx_sw().rcm_cc_overlap;
   bool counters_read = false;
   // (in two halves: on the side stream each half is enqueued behind one of the tie-break's ~45 us kernels)
   auto enqueue_cc_kernels = [&](int half) -> int {

@@ -76,3 +76,46 @@ def test_product_does_not_touch_the_oracle():
                 if re.search(r"sbx_oracle|libsbref|orc_[a-z_]+\(|oracle/", text):
                     bad.append(os.path.join(dirpath, f))
     assert not bad, bad
+
+
+def switch_reader():
+    # sbx_sw() in sbx_handle.hip: the library's one reader of the environment (the function's text, to its closing brace)
+    text = open(os.path.join(ROOT, "sparsebase_amd", "csrc", "sbx_handle.hip")).read()
+    start = text.index("const sbx_switches &sbx_sw() {")
+    return text[start:text.index("\n}\n", start) + 3]
+
+
+def test_environment_is_read_in_one_function():
+    reader = switch_reader()
+    hits = []
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "sparsebase_amd", "csrc")):
+        for f in files:
+            text = open(os.path.join(dirpath, f), errors="ignore").read()
+            if f == "sbx_handle.hip":
+                text = text.replace(reader, "")
+            if "getenv" in text:
+                hits.append(os.path.join(dirpath, f))
+    assert "getenv" in reader and not hits, hits
+
+
+def test_library_switches_are_the_readme_table():
+    read = re.findall(r'"(SBX_[A-Z0-9_]+)"', switch_reader())
+    assert len(read) == len(set(read)), "a switch read twice"
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    table = readme[readme.index("| library switch |"):]
+    table = table[:table.index("\n\n")]
+    listed = [re.search(r"`(SBX_[A-Z0-9_]+)", row).group(1) for row in table.splitlines()[2:]]
+    assert read == listed
+
+
+def test_no_tuning_build_is_left():
+    bad = []
+    for top in ("sparsebase_amd", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            if os.sep + "lib" in dirpath or "__pycache__" in dirpath:
+                continue
+            for f in files:
+                text = open(os.path.join(dirpath, f), errors="ignore").read()
+                if "SBX_TUNING" in text or "sbx_env_tuning" in text:
+                    bad.append(os.path.join(dirpath, f))
+    assert not bad, bad

@@ -16,7 +16,7 @@ if "--rcm" in sys.argv:
 else:
     perm = torch.randperm(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)).to(torch.int32)
 if "--prerelabel" in sys.argv:
-    # sort-only ablation (with SBX_PERMUTE_FORCE_RADIX=4: the kernels skip the relabel gathers): the columns arrive relabelled,
+    # sort-only ablation (a variant built with -DSBX_PERMUTE_ABLATE=4: the kernels skip the relabel gathers): the columns arrive relabelled,
     # so the sort sees the keys of the real call and no gather is issued
     col = perm[col.long()].contiguous()
 out = (torch.empty_like(rp), torch.empty_like(col), torch.empty_like(val))
