@@ -374,6 +374,53 @@ int sbx_rcm_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz,
                     sbx_rcm_stats *stats_host /* may be NULL */);
 
 /* ------------------------------------------------------------------ *
+ * A7b SlashburnReorder::GetReorderCSR — reorder/slashburn_reorder.cc:296-419 (+ :41-294)
+ * inv_perm_out[old] = new for the n = dimensions[0] vertices of a CSR whose rows may be unsorted and hold duplicates
+ * and self loops; the matrix may be rectangular as long as every column is below n.  Every walk runs over the
+ * symmetrized adjacency S of :333-376, entries counted with their multiplicity: row i of S is row i's stored entries
+ * in stored order, then, for every stored entry (r, i) whose r is not among row i's stored columns, r once per such
+ * entry, in descending r.  Placing a component C from a root p (orderCC :191-222) is a FIFO BFS over S limited to C
+ * (a vertex is enqueued when first seen, in its parent's adjacency order); the j-th vertex enqueued (p: j = 0) goes to
+ * P - j, P = n - 1 - (vertices placed from the back so far).
+ *   phase 0  components of S, each rooted at its smallest id, sorted by (size, root); all but the last are placed in
+ *            that order; the last, G, is placed from its root if |G| < k, else E = G and round t = 0 starts.
+ *   round t  deg(v) = the entries of row v of S whose column is in E.  The k hubs h_0 .. h_{k-1} go to t k + j.
+ *            Default: tau = the k-th largest degree in E, c = k - #{deg > tau}, T = the k-th vertex (id order) with
+ *            deg >= tau; the hubs are every deg > tau plus the LAST c (by id) of the degree-tau vertices with id <= T
+ *            (the closed form of removeKHubset's size-k heap, :108-158), in descending (deg, id) order.
+ *            SBX_SB_GREEDY (:41-106): k picks, each the smallest id of maximal current degree among E minus the picks
+ *            so far; after a pick h every entry (h, w) of S with w still eligible lowers deg(w) by one.
+ *            E' = E minus the hubs.  The scan runs the rows h_{k-1}, ..., h_0 of S; every component of S limited to
+ *            E' is rooted at the column of its first scan entry and takes that entry's hub index j.  The GCC is the
+ *            largest component, on equal sizes the one whose root entry comes first.  The others are placed in
+ *            ascending (SBX_SB_HUB_ORDER ? j : 0, size, root); then the GCC from its root if |GCC| < k (the end),
+ *            else E = GCC for round t + 1.  No component left ends the loop.
+ * Deliberate divergences from the reference:
+ *   - flags are this call's own: the reference keeps greedy / hub_order in process globals that a call can set but
+ *     never clears (:11-12, :309-312); the device computes the reference's value in a fresh process.
+ *   - k < 1 and columns outside [0, n) (out-of-range writes in the reference) are SBX_ERR_BAD_ARG; n = 0 (an empty
+ *     heap read) returns SBX_OK with nothing written.
+ *   - greedy picks use signed degrees for every index type (with unsigned ids the reference's seed degree[0] = -1
+ *     wraps, so vertex 0 always wins), and always pick from E: when vertex 0 is outside E and every eligible current
+ *     degree is negative (a hub row that holds w more often than w's row holds the hub), the reference's seed
+ *     (degree[0] = -1, 0) wins and vertex 0 is picked again.
+ *   - 2 nnz >= 2^31 (the reference's S offsets overflow IDType) and n >= 2^31 are SBX_ERR_UNSUPPORTED.
+ * Synchronous for status and statistics; inv_perm_out is complete in stream order.                                  */
+/* ------------------------------------------------------------------ */
+#define SBX_SB_GREEDY 0x1u    /* SlashburnReorderParams::greedy */
+#define SBX_SB_HUB_ORDER 0x2u /* SlashburnReorderParams::hub_order */
+typedef struct sbx_slashburn_stats {
+  int64_t rounds;             /* rounds of the slash loop (hub removals)                               */
+  int64_t hubs;               /* vertices placed as hubs: rounds x k                                   */
+  int64_t spoke_components;   /* components the rounds placed from the back, the final GCC excluded    */
+  int64_t initial_components; /* connected components of S (phase 0)                                   */
+  int64_t final_gcc;          /* size of the component placed last from its root (0: none was left)   */
+} sbx_slashburn_stats;
+int sbx_slashburn_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
+                          const void *col, int64_t k, unsigned flags, void *inv_perm_out,
+                          sbx_slashburn_stats *stats_host /* may be NULL */);
+
+/* ------------------------------------------------------------------ *
  * A8  GrayReorder::GrayReorderingCSR — reorder/gray_reorder.cc:106-424 *
  * Device stage: per-row degree, band count and Gray-decoded bitmap key. *
  * key_out[i] (uint64) = decoded bitmap of row i computed with the row's  *

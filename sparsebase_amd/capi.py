@@ -16,6 +16,7 @@ SBX_I32, SBX_I64, SBX_I32_N64 = 0, 1, 2
 V_NONE, V_I32, V_U32, V_F32, V_I64, V_U64, V_F64 = range(7)
 FLAG_MOVE, FLAG_ROWS_SORTED = 1, 2
 TC_DIRECTED, TC_EXACT = 1, 2
+SB_GREEDY, SB_HUB_ORDER = 1, 2
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -31,6 +32,10 @@ class RcmStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("components", "isolated", "small_components", "large_components",
                                          "bfs_sweeps", "bfs_levels", "edges_scanned", "edges_scanned_bottom_up",
                                          "largest_component", "reference_sweeps", "unordered_sweeps")]
+
+
+class SlashburnStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("rounds", "hubs", "spoke_components", "initial_components", "final_gcc")]
 
 
 # every symbol include/sbx.h declares (tests/test_abi.py checks header <-> library <-> this table)
@@ -87,6 +92,7 @@ PROTOTYPES = {
     "sbx_csr_triangle_count": ([_H, _int, _i64, _i64, _vp, _vp, _u, C.POINTER(_i64)], _int),
     "sbx_degree_reorder": ([_H, _int, _i64, _vp, _int, _vp], _int),
     "sbx_rcm_reorder": ([_H, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(RcmStats)], _int),
+    "sbx_slashburn_reorder": ([_H, _int, _i64, _i64, _vp, _vp, _i64, _u, _vp, C.POINTER(SlashburnStats)], _int),
     "sbx_gray_row_keys": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, C.POINTER(_i64)], _int),
     "sbx_gray_reorder": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _vp], _int),
     "sbx_inverse_permutation": ([_H, _int, _i64, _vp, _vp], _int),

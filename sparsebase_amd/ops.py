@@ -321,6 +321,22 @@ def rcm_reorder(row_ptr, col, out=None, return_stats=False):
     return inv
 
 
+def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
+    """reorder::SlashburnReorder of a CSR graph: inv[old] = new (the dtype of col).  k hubs per round; greedy and
+    hub_order are SlashburnReorderParams' flags, taken from this call alone.  See sbx_slashburn_reorder in
+    include/sbx.h for the rules."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    n = row_ptr.numel() - 1
+    inv = torch.empty(n, dtype=col.dtype, device=row_ptr.device) if out is None else out
+    stats = capi.SlashburnStats()
+    flags = (capi.SB_GREEDY if greedy else 0) | (capi.SB_HUB_ORDER if hub_order else 0)
+    hd.check(hd.lib.sbx_slashburn_reorder(hd.h, _it(row_ptr, col), n, col.numel(), _p(row_ptr), _p(col), int(k),
+                                          flags, _p(inv), C.byref(stats)))
+    if return_stats:
+        return inv, {k_: getattr(stats, k_) for k_, _ in capi.SlashburnStats._fields_}
+    return inv
+
+
 def gray_row_keys(m, row_ptr, col, resolution, nnz_threshold):
     hd = handle_for(_check_dev(row_ptr, col))
     n = row_ptr.numel() - 1
