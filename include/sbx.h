@@ -421,6 +421,52 @@ int sbx_slashburn_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t 
                           sbx_slashburn_stats *stats_host /* may be NULL */);
 
 /* ------------------------------------------------------------------ *
+ * A7c BOBAReorder::GetReorderCOO — reorder/boba_reorder.cc:33-138
+ * inv_perm_out[old] = new for the nodes = max(n, m) vertices of a COO (row[], col[]: nnz entries, in any order,
+ * duplicates and self loops allowed; the reference takes any id below nodes, so rows in [n, nodes) are accepted too).
+ * The reference sorts the entries by (col, row) and numbers the vertices in order of first appearance, in the row
+ * array, then in the column array, then the rest; in closed form the new order is three groups, one after the other:
+ *   1. vertices with an entry in their row, by (mincol(v), v), mincol(v) = the smallest column of row v;
+ *   2. vertices without a row entry that occur as a column, by id;
+ *   3. every other vertex, by id.
+ * BOBAReorderParams::sequential does not change this order (both of the reference's modes compute it), so the entry
+ * point takes no flag.  The COO has no offset array: SBX_I32_N64 is SBX_I32 here, and nnz may be of any size.
+ * Deliberate divergences from the reference:
+ *   - the parallel mode's `omp parallel for` (:119) updates order[] with an unguarded read-compare-write, so with
+ *     several threads it can keep a position that is not the first; its sentinel nnz * 2 is computed in IDType and
+ *     overflows for nnz >= 2^30 with 32-bit ids; both modes loop with int over std::pair<int, int> copies of the
+ *     entries.  Parity holds for ids and nnz below 2^31, and for the parallel mode where it runs race-free.
+ *   - an id outside [0, max(n, m)) (an out-of-range write in the reference) is SBX_ERR_BAD_ARG, and nothing is
+ *     written; max(n, m) >= 2^31 is SBX_ERR_UNSUPPORTED.
+ * Synchronous for status; inv_perm_out is complete in stream order.                                                 */
+/* ------------------------------------------------------------------ */
+int sbx_boba_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t m, int64_t nnz, const void *row,
+                     const void *col, void *inv_perm_out /* max(n, m) entries */);
+
+/* ------------------------------------------------------------------ *
+ * A7d ReorderHeatmap::ReorderHeatmapCSRArrayArray — reorder/reorder_heatmap.cc:43-119 (ReorderBase::Heatmap,
+ * bases/reorder_base.h:696).  The share of the nonzeros of an n x m CSR (nnz = row_ptr[n]) in each block of a
+ * b x b grid (b = num_parts) once the rows are placed by order_r (n entries) and the columns by order_c (m entries),
+ * both orders giving new positions.  With bsize = n / b (the row count for both axes, as in the reference), every
+ * entry (i, c) counts in cell (bu, bv), bu = min(order_r[i] / bsize, b - 1), bv = min(order_c[c] / bsize, b - 1);
+ *   heat_out[bu * b + bv] = (float)count / (float)nnz
+ * a correctly rounded fp32 division, widened when FeatureType is double (feature_bytes 8; float: 4), so an empty
+ * matrix gives NaN in every cell.  heat_out: b * b values on the device.  The cell counters are 64-bit, so a cell
+ * may hold any number of entries.  The reference's max_bw, mean_bw and fblocks are computed there and discarded;
+ * they are not computed here.
+ * Deliberate divergences from the reference:
+ *   - b < 1 (b = 0 divides by zero in the reference), b > n and b > m are SBX_ERR_BAD_ARG (the reference throws
+ *     ReorderException for b > n or b > m, and for negative b, which it compares as unsigned).
+ *   - a column outside [0, m) or a negative entry of order_r or order_c (out-of-range reads and writes in the
+ *     reference) is SBX_ERR_BAD_ARG, and heat_out is not written.
+ *   - the counts are exact in 64 bits (the reference counts in NNZType).
+ * b * b counters that cannot be allocated give SBX_ERR_OOM.  Synchronous.                                         */
+/* ------------------------------------------------------------------ */
+int sbx_csr_reorder_heatmap(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t m, int64_t nnz,
+                            const void *row_ptr, const void *col, const void *order_r, const void *order_c,
+                            int64_t num_parts, int feature_bytes, void *heat_out /* num_parts^2 values */);
+
+/* ------------------------------------------------------------------ *
  * A8  GrayReorder::GrayReorderingCSR — reorder/gray_reorder.cc:106-424 *
  * Device stage: per-row degree, band count and Gray-decoded bitmap key. *
  * key_out[i] (uint64) = decoded bitmap of row i computed with the row's  *

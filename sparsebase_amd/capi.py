@@ -93,6 +93,8 @@ PROTOTYPES = {
     "sbx_degree_reorder": ([_H, _int, _i64, _vp, _int, _vp], _int),
     "sbx_rcm_reorder": ([_H, _int, _i64, _i64, _vp, _vp, _vp, C.POINTER(RcmStats)], _int),
     "sbx_slashburn_reorder": ([_H, _int, _i64, _i64, _vp, _vp, _i64, _u, _vp, C.POINTER(SlashburnStats)], _int),
+    "sbx_boba_reorder": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _vp], _int),
+    "sbx_csr_reorder_heatmap": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp], _int),
     "sbx_gray_row_keys": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, C.POINTER(_i64)], _int),
     "sbx_gray_reorder": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _vp], _int),
     "sbx_inverse_permutation": ([_H, _int, _i64, _vp, _vp], _int),

@@ -8,6 +8,7 @@
 #include "sparsebase/reorder/generic_reorder.h"
 #include "sparsebase/reorder/gray_reorder.h"
 #include "sparsebase/reorder/rcm_reorder.h"
+#include "sparsebase/reorder/reorder_heatmap.h"
 
 namespace sparsebase::bases {
 
@@ -169,6 +170,20 @@ class ReorderBase {
     if constexpr (std::is_same_v<Ret<V>, format::FormatOrderOne<V>>) return out;
     else if (convert_output) return out->template Convert<Ret>();
     else return out->template As<Ret>();
+  }
+
+  // the share of the nonzeros in each cell of a num_parts x num_parts grid after the row and column orders (reference
+  // :696; reorder::ReorderHeatmap): a host Array<FloatType> the caller owns
+  template <typename FloatType, typename I, typename N, typename V>
+  static format::Array<FloatType> *Heatmap(F2<I, N, V> *format, format::FormatOrderOne<I> *permutation_r,
+                                           format::FormatOrderOne<I> *permutation_c, int num_parts,
+                                           std::vector<context::Context *> contexts, bool convert_input) {
+    reorder::ReorderHeatmap<I, N, V, FloatType> heatmapper(num_parts);
+    std::unique_ptr<format::FormatOrderOne<FloatType>> arr(
+        heatmapper.Get(format, permutation_r, permutation_c, contexts, convert_input));
+    if (arr->template IsAbsolute<format::Array<FloatType>>())
+      return static_cast<format::Array<FloatType> *>(arr.release());
+    return arr->template Convert<format::Array>();
   }
 
   // inv[perm[i]] = i on the GPU (reference :663-672); result is a host new[] array

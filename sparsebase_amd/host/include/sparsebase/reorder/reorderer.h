@@ -101,6 +101,44 @@ struct DeviceCsrView {
     staged = false;
   }
 };
+// A COO's index arrays on a device: borrowed from an HIPCOO, or staged from a host COO.
+template <typename I, typename N, typename V>
+struct DeviceCooView {
+  hip::Device *dev = nullptr;
+  I n = 0, m = 0;
+  int64_t nnz = 0;
+  I *row = nullptr;
+  I *col = nullptr;
+  bool staged = false;
+
+  static DeviceCooView Borrow(format::HIPCOO<I, N, V> *d) {
+    DeviceCooView v;
+    v.dev = &d->device();
+    v.n = (I)d->get_dimensions()[0];
+    v.m = (I)d->get_dimensions()[1];
+    v.nnz = (int64_t)d->get_num_nnz();
+    v.row = d->get_row();
+    v.col = d->get_col();
+    return v;
+  }
+  static DeviceCooView Stage(format::COO<I, N, V> *h) {
+    DeviceCooView v;
+    v.dev = &hip::Device::Get(hip::DefaultDevice());
+    v.n = (I)h->get_dimensions()[0];
+    v.m = (I)h->get_dimensions()[1];
+    v.nnz = (int64_t)h->get_num_nnz();
+    v.row = v.dev->Upload(h->get_row(), (size_t)(v.nnz ? v.nnz : 1));
+    v.col = v.dev->Upload(h->get_col(), (size_t)(v.nnz ? v.nnz : 1));
+    v.staged = true;
+    return v;
+  }
+  void Release() {
+    if (!staged) return;
+    dev->Free(row);
+    dev->Free(col);
+    staged = false;
+  }
+};
 }  // namespace detail
 
 }  // namespace sparsebase::reorder

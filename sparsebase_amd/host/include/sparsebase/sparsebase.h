@@ -17,6 +17,8 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/reorder/boba_reorder.h"
+#include "sparsebase/reorder/reorder_heatmap.h"
 #include "sparsebase/reorder/slashburn_reorder.h"
 #include "sparsebase/utils/logger.h"
 // last: the reader needs the complete conversion graph

@@ -92,6 +92,12 @@ class AttemptToReset : public Exception {
   AttemptToReset() : Exception("Attempt to reset a once-settable value") {}
 };
 
+// Thrown by the reorder module (reference :52), e.g. ReorderHeatmap with num_parts out of range.
+class ReorderException : public Exception {
+ public:
+  explicit ReorderException(const std::string &msg) : Exception(msg) {}
+};
+
 // Device errors: the HIP analogue of the reference's CUDADeviceException (:178).
 class HIPDeviceException : public Exception {
  public:

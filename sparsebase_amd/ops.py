@@ -337,6 +337,33 @@ def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, 
     return inv
 
 
+def boba_reorder(row, col, n, m, out=None):
+    """reorder::BOBAReorder of an n x m COO (row, col: the entries in any order): inv[old] = new for the max(n, m)
+    vertices (the dtype of row).  See sbx_boba_reorder in include/sbx.h for the rule."""
+    hd = handle_for(_check_dev(row, col))
+    if row.dtype != col.dtype:
+        raise TypeError("row and col must share one dtype")
+    nodes = max(int(n), int(m))
+    inv = torch.empty(nodes, dtype=row.dtype, device=row.device) if out is None else out
+    hd.check(hd.lib.sbx_boba_reorder(hd.h, _it(row), int(n), int(m), row.numel(), _p(row), _p(col), _p(inv)))
+    return inv
+
+
+def csr_reorder_heatmap(row_ptr, col, order_r, order_c, num_parts, m=None, double=False):
+    """reorder::ReorderHeatmap of an n x m CSR placed by order_r (n new row positions) and order_c (m new column
+    positions): a device tensor of num_parts^2 float32 (double=True: float64) nonzero shares, cell (i, j) at
+    i * num_parts + j.  m defaults to n.  See sbx_csr_reorder_heatmap in include/sbx.h for the rule."""
+    hd = handle_for(_check_dev(row_ptr, col, order_r, order_c))
+    n = row_ptr.numel() - 1
+    m = n if m is None else int(m)
+    b = int(num_parts)
+    cells = b * b if 1 <= b <= min(n, m) else 0  # (an out-of-range b is the library's to refuse)
+    out = torch.empty(cells, dtype=torch.float64 if double else torch.float32, device=row_ptr.device)
+    hd.check(hd.lib.sbx_csr_reorder_heatmap(hd.h, _it(row_ptr, col), n, m, col.numel(), _p(row_ptr), _p(col),
+                                            _p(order_r), _p(order_c), b, out.element_size(), _p(out)))
+    return out
+
+
 def gray_row_keys(m, row_ptr, col, resolution, nnz_threshold):
     hd = handle_for(_check_dev(row_ptr, col))
     n = row_ptr.numel() - 1
