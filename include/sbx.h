@@ -23,7 +23,12 @@
  *    pointers are final when they return — their device outputs keep the
  *    stream-order guarantee and no more (sbx_rcm_reorder and
  *    sbx_gray_reorder return with their last kernel enqueued, not finished).
- *    All other functions return as soon as the work is enqueued.
+ *    The functions NOT documented as synchronous return as soon as the work is
+ *    enqueued: sbx_csr_to_coo, sbx_coo_to_csr with SBX_FLAG_ROWS_SORTED and
+ *    32-bit ids, sbx_csr_degrees, sbx_csr_degree_distribution,
+ *    sbx_csr_jaccard_weights, sbx_inverse_permutation, sbx_permute_array
+ *    ("Streams", has the table, which
+ *    tests/test_stream_order_gpu.py asserts on a caller's stream).
  *  - Return value: SBX_OK (0) or an sbx_status error code; nothing throws
  *    across this boundary.  sbx_last_error() gives a message for the last
  *    failing call on the handle.
@@ -107,7 +112,7 @@ typedef enum sbx_value_type {
  *                                                                      *
  * Streams: every entry point enqueues its work on the handle's stream  *
  * (sbx_set_stream; default: the null stream).  Some entry points run    *
- * independent stages on up to two private side streams of the handle;  *
+ * independent stages on private side streams of the handle (seven);    *
  * those fork from and are joined back into the handle's stream by      *
  * events before the call returns, so callers order against the         *
  * handle's stream only.  A handle serves one host thread at a time.    */
@@ -177,14 +182,20 @@ int sbx_coo_sort(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n
 int sbx_csr_rows_sorted(sbx_handle_t h, sbx_index_type it, int64_t n, const void *row_ptr,
                         const void *col, int *sorted_host);
 /* If any row is unsorted, sort EVERY row by (col,val) in place
- * (format/csr.cc:118-157); otherwise leave the arrays untouched. */
+ * (format/csr.cc:118-157); otherwise leave the arrays untouched.
+ * Synchronous for status (the test of sbx_csr_rows_sorted is read back);
+ * col / val are complete in stream order. */
 int sbx_csr_sort_rows(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n,
                       int64_t m, int64_t nnz, const void *row_ptr, void *col, void *val);
 
 /* ------------------------------------------------------------------ *
  * A2/A2m  COO -> CSR — converter/converter_order_two.cc:163-212, :215-246
  * row_ptr_out = exclusive scan of the row histogram; col/val copied verbatim.
- * With SBX_FLAG_MOVE col_out/val_out are ignored (may be NULL).         */
+ * With SBX_FLAG_MOVE col_out/val_out are ignored (may be NULL).
+ * Synchronous for status (whether row[] is sorted is read back; SBX_I64 reads
+ * back a range check of the row ids first) — except with SBX_FLAG_ROWS_SORTED
+ * and 32-bit ids (SBX_I32, SBX_I32_N64), which returns with the work enqueued.
+ * The outputs are complete in stream order either way.                  */
 /* ------------------------------------------------------------------ */
 int sbx_coo_to_csr(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m,
                    int64_t nnz, const void *row, const void *col, const void *val,
@@ -203,7 +214,8 @@ int sbx_csr_to_coo(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t
  * CSC constructor does (format/csc.cc:99-157: if any column's rows are out of order, every
  * column's (row, value) pairs are sorted).  col_ptr_out has m + 1 entries; the reference
  * sizes it by the ROW count (:32-33) and is only safe for n == m, where the two agree.
- * A15  CSR -> CSC — :120-128: CSR -> COO -> CSC (the transpose when rows are sorted). */
+ * A15  CSR -> CSC — :120-128: CSR -> COO -> CSC (the transpose when rows are sorted).
+ * Both synchronous for status (the conversions and checks inside read back); outputs complete in stream order. */
 /* ------------------------------------------------------------------ */
 int sbx_coo_to_csc(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m,
                    int64_t nnz, const void *row, const void *col, const void *val,
@@ -234,7 +246,7 @@ int sbx_mtx_parse_coordinate(sbx_handle_t h, sbx_index_type it, sbx_value_type v
                              int symmetry, unsigned flags, int64_t capacity, void *row_out, void *col_out,
                              void *val_out, int64_t *nnz_host);
 
-/* Number of whitespace-separated tokens in a device text buffer (to size the parsers' outputs). */
+/* Number of whitespace-separated tokens in a device text buffer (to size the parsers' outputs).  Synchronous. */
 int sbx_text_count_tokens(sbx_handle_t h, const void *text_dev, int64_t bytes, int64_t *tokens_host);
 
 /* ------------------------------------------------------------------ *
@@ -264,7 +276,8 @@ int sbx_edge_list_parse(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, co
  *   sbx_csr_bandwidth            feature/bandwidth.cc:93-112    max over nonzeros of |i - j| + 1 (0 if none)
  *   sbx_csr_profile              feature/profile.cc:91-105      sum over rows of i - min(i, smallest column);
  *                                returned exactly in 64 bits (the reference accumulates in IDType)
- * The two scalar results are written to host memory; the calls are synchronous.            */
+ * The two scalar results are written to host memory: sbx_csr_bandwidth and sbx_csr_profile are synchronous;
+ * sbx_csr_degrees and sbx_csr_degree_distribution return with their kernel enqueued.      */
 /* ------------------------------------------------------------------ */
 int sbx_csr_degrees(sbx_handle_t h, sbx_index_type it, int64_t n, const void *row_ptr, void *degrees_out);
 int sbx_csr_degree_distribution(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz,
@@ -285,7 +298,8 @@ int sbx_csr_profile(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, c
  * Every position those writes miss (asymmetric patterns, duplicate entries the search does not land on), which the
  * reference leaves uninitialised, gets the weight of its own (row, column) pair computed the same way.  Columns
  * outside [0, n) read as rows without entries.  Degrees must be below 2^31 (else SBX_ERR_UNSUPPORTED).  Complete in
- * stream order on the handle's stream, like sbx_csr_degree_distribution.                                           */
+ * stream order on the handle's stream, like sbx_csr_degree_distribution: the call returns with its kernels enqueued
+ * (only nnz >= 2^31 reads the largest degree back first).                                                          */
 int sbx_csr_jaccard_weights(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
                             const void *col, int feature_bytes, void *weights_out);
 
@@ -316,7 +330,8 @@ int sbx_csr_triangle_count(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t
 /* ------------------------------------------------------------------ *
  * A6  DegreeReorder::CalculateReorderCSR — reorder/degree_reorder.cc:22-62
  * inv_perm_out[old_row] = new_row; ascending: (deg asc, id desc),        *
- * descending: the exact reverse.                                         */
+ * descending: the exact reverse.  Synchronous for status (the counting    *
+ * pass's totals are read back); inv_perm_out complete in stream order.   */
 /* ------------------------------------------------------------------ */
 int sbx_degree_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, const void *row_ptr,
                        int ascending, void *inv_perm_out);
@@ -510,8 +525,11 @@ int sbx_inverse_permutation(sbx_handle_t h, sbx_index_type it, int64_t n, const 
  * sbx_permute_csr_rows produces only new rows [row_begin,row_end): row_ptr_out
  * receives row_end-row_begin+1 entries rebased to 0, col_out/val_out the
  * shard's nonzeros; *shard_nnz_host gets the shard's nnz.  The row-range
- * split is the multi-GPU decomposition.  Synchronous only
- * when shard_nnz_host != NULL.                                           */
+ * split is the multi-GPU decomposition.  Both synchronous
+ * for status and *shard_nnz_host, with or without that pointer (the shard's
+ * size and row classes, or the row-wise copy's sortedness flag, are read
+ * back); the output arrays are complete in stream order — their last kernels,
+ * side streams joined, are enqueued behind the last read-back.           */
 /* ------------------------------------------------------------------ */
 int sbx_permute_csr(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m,
                     int64_t nnz, const void *row_ptr, const void *col, const void *val,
@@ -524,7 +542,7 @@ int sbx_permute_csr_rows(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, i
                          void *val_out, int64_t out_capacity, int64_t *shard_nnz_host);
 
 /* PermuteOrderOne::PermuteArray — permute/permute_order_one.cc:18-37:
- * out[order[i]] = vals[i]. */
+ * out[order[i]] = vals[i].  Returns with its kernel enqueued (as does sbx_inverse_permutation). */
 int sbx_permute_array(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n,
                       const void *order, const void *vals, void *out);
 
@@ -552,7 +570,7 @@ int sbx_comm_create_rccl(int device, int rank, int world, const void *unique_id,
 int sbx_comm_rank(sbx_comm_t comm, int *rank, int *world);
 int sbx_comm_destroy(sbx_comm_t comm);
 
-/* Entries of the new rows [row_begin,row_end): what a rank's col_out / val_out must hold. */
+/* Entries of the new rows [row_begin,row_end): what a rank's col_out / val_out must hold.  Synchronous. */
 int sbx_permute_csr_rows_nnz(sbx_handle_t h, sbx_index_type it, int64_t n, const void *row_ptr,
                              const void *row_order, int64_t row_begin, int64_t row_end,
                              int64_t *nnz_host);

@@ -73,7 +73,10 @@ def build(force=False, verbose=False):
 
 # Checking builds that travel with the product library (built by __graft_entry__.build(), loaded only by tests):
 #   fenced: sbx_rcm.hip with -DSBX_GB_FENCED — release / acquire fences at every grid barrier and election (see gb_wait)
-VARIANTS = {"fenced": (("sbx_rcm.hip", "sbx_rcm64.hip"), ["-DSBX_GB_FENCED"])}
+#   stream0: sbx_features.hip with -DSBX_DEBUG_DEGREES_STREAM0=1 — sbx_csr_degrees launches on the null stream instead of
+#            the handle's: the deliberate wrong-stream bug tests/test_stream_order_gpu.py has to report
+VARIANTS = {"fenced": (("sbx_rcm.hip", "sbx_rcm64.hip"), ["-DSBX_GB_FENCED"]),
+            "stream0": (("sbx_features.hip",), ["-DSBX_DEBUG_DEGREES_STREAM0=1"])}
 
 
 def variant_path(name):

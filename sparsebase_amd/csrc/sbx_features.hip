@@ -314,12 +314,21 @@ int expand_rows(sbx_handle_t h, int64_t n, int64_t nnz, const I *rp, I **rows) {
     if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
   } while (0)
 
+#ifndef SBX_DEBUG_DEGREES_STREAM0
+#define SBX_DEBUG_DEGREES_STREAM0 0  // 1: k_degrees goes to the null stream instead of the handle's (the wrong-stream build
+#endif                               // tests/test_stream_order_gpu.py must catch: sparsebase_amd/build.py, VARIANTS)
+
 template <typename I, typename D = I>
 static int csr_degrees_typed(sbx_handle_t h, int64_t n, const void *row_ptr, void *degrees_out) {
   SBX_TRY(sbx_arena_begin(h));
   if (n == 0) return SBX_OK;
+#if SBX_DEBUG_DEGREES_STREAM0
+  hipLaunchKernelGGL((k_degrees<I, D>), dim3(sbx_grid_for(n, FT_THREADS, 8192)), dim3(FT_THREADS), 0, (hipStream_t) nullptr,
+                     (const I *)row_ptr, (D *)degrees_out, n);
+#else
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_degrees<I, D>), dim3(sbx_grid_for(n, FT_THREADS, 8192)), dim3(FT_THREADS), (const I *)row_ptr,
               (D *)degrees_out, n);
+#endif
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_FEATURE, 2 * (int64_t)sizeof(I) * n + (int64_t)sizeof(I));
   return SBX_OK;

@@ -200,6 +200,21 @@ int sbx_aux_streams(sbx_handle_t h) {
   return SBX_OK;
 }
 
+void sbx_aux_join(sbx_handle_t h, hipStream_t main_stream) {
+  if (h->aux_ready) {
+    bool ok = true;
+    for (int i = 0; i < SBX_AUX_STREAMS; i++)
+      ok = ok && hipEventRecord(h->aux_event[1 + i], h->aux_stream[i]) == hipSuccess &&
+           hipStreamWaitEvent(main_stream, h->aux_event[1 + i], 0) == hipSuccess;
+    if (!ok) {  // no event to order by: the host waits instead
+      (void)hipGetLastError();
+      for (int i = 0; i < SBX_AUX_STREAMS; i++) (void)hipStreamSynchronize(h->aux_stream[i]);
+    }
+  }
+  h->aux_dirty = false;
+  h->rs_override = nullptr;
+}
+
 extern "C" int sbx_set_stream(sbx_handle_t h, void *hip_stream) {
   if (!h) return SBX_ERR_BAD_ARG;
   if (h->stream != (hipStream_t)hip_stream) {

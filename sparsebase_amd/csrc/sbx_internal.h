@@ -84,7 +84,7 @@ struct sbx_handle_s {
   hipStream_t aux_stream[SBX_AUX_STREAMS];
   hipEvent_t aux_event[SBX_AUX_STREAMS + 1];
   bool aux_ready;
-  bool aux_dirty;     // a side stream may still be running work of a call that returned early (error path)
+  bool aux_dirty;     // a fork onto the side streams is open: set at the fork, cleared by the join (sbx_aux_scope)
   bool rs_tied_hint;  // set around a sort whose keys are heavily tied (Gray's composite keys): k_onesweep_hist aggregates per wave
   void *rs_override;  // next radix sort takes this zeroed slot instead of one from the pool (sorts on a side stream
                       // must not share the pool with the main stream: the pool is re-zeroed in stream order)
@@ -100,6 +100,24 @@ struct sbx_handle_s {
 };
 
 int sbx_aux_streams(sbx_handle_t h);  // creates aux_stream / aux_event if needed
+// joins every side stream back into `main_stream` (an event behind whatever each one holds, waited for by `main_stream`)
+// and clears aux_dirty: what a call does that leaves between a fork and its join
+void sbx_aux_join(sbx_handle_t h, hipStream_t main_stream);
+// Held by every function that is the outermost one to fork work onto the side streams: whichever way the call leaves it
+// — the end, SBX_TRY, SBX_FAIL, a successful early return — a fork that is still open (aux_dirty) is joined into the
+// caller's stream first, and h->stream is the caller's again.  The joins on the paths that succeed stay where they are
+// (they clear aux_dirty); this is the net under all the others.
+struct sbx_aux_scope {
+  sbx_handle_t h;
+  hipStream_t main_stream;
+  explicit sbx_aux_scope(sbx_handle_t h_) : h(h_), main_stream(h_->stream) {}
+  ~sbx_aux_scope() {
+    h->stream = main_stream;
+    if (h->aux_dirty) sbx_aux_join(h, main_stream);
+  }
+  sbx_aux_scope(const sbx_aux_scope &) = delete;
+  sbx_aux_scope &operator=(const sbx_aux_scope &) = delete;
+};
 void sbx_prof_begin(sbx_handle_t h, int kid);
 void sbx_prof_end(sbx_handle_t h);
 

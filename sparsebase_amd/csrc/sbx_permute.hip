@@ -3084,6 +3084,7 @@ static int permute_csr_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, 
   const int vb = (val && val_out) ? sbx_value_bytes(vt) : 0;
   SBX_REQUIRE(h, vb >= 0, "unknown value type");
   SBX_TRY(sbx_arena_begin(h));
+  sbx_aux_scope aux_scope(h);  // (the map's fork below and the sort stage's: no way out of this function leaves one open)
   const int64_t nr = row_end - row_begin;
   I *rpo = (I *)row_ptr_out;
   if (shard_nnz_host) *shard_nnz_host = 0;
@@ -3233,6 +3234,7 @@ int sbx_sort_segments(sbx_handle_t h, int vb, int64_t nseg, int64_t key_limit, i
   int2 *rec = nullptr;
   const int block_cap = vb == 8 ? BlockRowCap<8>::value : BlockRowCap<4>::value;
   unsigned long long *status = nullptr;
+  sbx_aux_scope aux_scope(h);  // (the sort stage forks)
   SBX_TRY(perm_prep_alloc(h, nseg, &st, &status, &rec));
   SBX_TRY(sbx_salloc(h, (size_t)nseg, &long_rows));
   SBX_TRY(sbx_salloc(h, (size_t)nseg * BR_CLASSES, &block_rows));
@@ -3267,6 +3269,7 @@ static int csr_sort_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, int
   const int vb = val ? sbx_value_bytes(vt) : 0;
   SBX_REQUIRE(h, vb >= 0, "unknown value type");
   SBX_TRY(sbx_arena_begin(h));
+  sbx_aux_scope aux_scope(h);  // (the sort stage forks)
   PermState *st = nullptr;
   I *long_rows = nullptr, *block_rows = nullptr, *ctmp = nullptr;
   int2 *rec = nullptr;

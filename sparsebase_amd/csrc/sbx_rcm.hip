@@ -4087,6 +4087,7 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
                   sbx_rcm_stats *stats_host) {
   if (stats_host) memset(stats_host, 0, sizeof(*stats_host));
   SBX_TRY(sbx_arena_begin(h));
+  sbx_aux_scope aux_scope(h);  // (degree ranks, component labelling, split expansion: no way out leaves a fork open)
   if (n == 0) return SBX_OK;
   const X *rp = (const X *)row_ptr, *col = (const X *)col_v;
   X *inv = (X *)inv_perm_out;
