@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sbx.h (sparsebase_amd/lib/libsbx.so).
+"""ctypes binding of the C ABI in include/sbx.h and include/sbx_text.h (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
 usable, loading / handle creation raises.  torch is used only as the owner of
@@ -17,6 +17,7 @@ V_NONE, V_I32, V_U32, V_F32, V_I64, V_U64, V_F64 = range(7)
 FLAG_MOVE, FLAG_ROWS_SORTED = 1, 2
 TC_DIRECTED, TC_EXACT = 1, 2
 SB_GREEDY, SB_HUB_ORDER = 1, 2
+TEXT_LOWER, TEXT_NO_DIAGONAL, TEXT_PATTERN = 1, 2, 4
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -117,6 +118,16 @@ PROTOTYPES = {
     "sbx_balanced_row_splits": ([_H, _int, _i64, _vp, _vp, _int, C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbx_text.h declares (tests/test_text_abi.py checks header <-> library <-> this table); a table of
+# its own, as the header is a header of its own: PROTOTYPES stays the table of include/sbx.h
+TEXT_PROTOTYPES = {
+    "sbx_text_format_values": ([_H, _int, _i64, _vp, _int, _vp, _i64, C.POINTER(_i64)], _int),
+    "sbx_text_format_coordinate": ([_H, _int, _int, _i64, _vp, _vp, _vp, _i64, _int, _u, _vp, _i64, C.POINTER(_i64)], _int),
+    "sbx_coo_symmetry_check": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _int, C.POINTER(_i64)], _int),
+    "sbx_coo_undirected_unique": ([_H, _int, _int, _i64, _vp, _vp, _vp, C.POINTER(_i64)], _int),
+    "sbx_text_format_dense": ([_H, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -128,7 +139,7 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: run `python -m sparsebase_amd.build` "
                               "(there is no CPU fallback for the HIP hot path)")
         lib = C.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in PROTOTYPES.items():
+        for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

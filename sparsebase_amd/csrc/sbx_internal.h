@@ -39,6 +39,10 @@ enum sbx_kernel_id {
   SBX_K_FEATURE,
   SBX_K_MTX,
   SBX_K_MISC,
+  SBX_K_TEXT_FORMAT,
+  SBX_K_TEXT_LONG,
+  SBX_K_TEXT_WRITE,
+  SBX_K_TEXT_CHECK,
   SBX_K_COUNT
 };
 extern const char *const sbx_kernel_names[SBX_K_COUNT];
@@ -306,6 +310,10 @@ int sbx_radix_sort_emit(sbx_handle_t h, void *keys_a, void *keys_b, int64_t coun
                         int num_passes, const sbx_radix_emit *emit);
 
 int sbx_fill_i32(sbx_handle_t h, int32_t *dst, int32_t value, int64_t count);
+
+// the handle's device table of 5^k limbs and Eisel-Lemire significands (sbx_dec2bin.h: SBX_TABLE_WORDS words), built on
+// first use (sbx_mtx.hip); the parsers and the text formatters (sbx_text.hip) share it
+int sbx_pow5_table(sbx_handle_t h, const uint64_t **out);
 
 // degree ranks of the non-empty rows, (degree, id) ascending, both ways (sbx_degree.hip; for the RCM's Cuthill-McKee keys);
 // n_top = rows of 255 entries and more; enqueued on h->stream, scratch from the running call's arena, no read-back

@@ -298,6 +298,8 @@ static int mx_pow5(sbx_handle_t h, const uint64_t **out) {
   return SBX_OK;
 }
 
+int sbx_pow5_table(sbx_handle_t h, const uint64_t **out) { return mx_pow5(h, out); }
+
 extern "C" int sbx_mtx_parse_coordinate(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, const void *text_dev,
                                         int64_t bytes, int64_t n_rows, int64_t n_cols, int64_t entries, int fields,
                                         int symmetry, unsigned flags, int64_t capacity, void *row_out, void *col_out,

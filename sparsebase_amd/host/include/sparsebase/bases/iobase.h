@@ -8,7 +8,9 @@
 #include "sparsebase/io/binary_writer_order_one.h"
 #include "sparsebase/io/binary_writer_order_two.h"
 #include "sparsebase/io/edge_list_reader.h"
+#include "sparsebase/io/edge_list_writer.h"
 #include "sparsebase/io/mtx_reader.h"
+#include "sparsebase/io/mtx_writer.h"
 
 namespace sparsebase::bases {
 

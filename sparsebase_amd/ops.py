@@ -598,3 +598,78 @@ def _equal_range(n, world, rank):
     base, extra = divmod(n, world)
     lo = rank * base + min(rank, extra)
     return lo, lo + base + (1 if rank < extra else 0)
+
+
+# ----------------------------------------------------------------------------- text output (include/sbx_text.h)
+def _text_vt(val, unsigned):
+    vt = _vt(val)
+    if unsigned:
+        if vt not in (capi.V_I32, capi.V_I64):
+            raise TypeError("unsigned=True reads an int32 / int64 tensor as uint32 / uint64")
+        vt = capi.V_U32 if vt == capi.V_I32 else capi.V_U64
+    return vt
+
+
+def _text_two_calls(hd, device, call):
+    """The formatters' protocol: the sizing call, the allocation, the writing call; a uint8 tensor of the exact length."""
+    nbytes = C.c_int64(0)
+    hd.check(call(None, 0, nbytes))
+    text = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    if nbytes.value:
+        wrote = C.c_int64(0)
+        hd.check(call(_p(text), nbytes.value, wrote))
+        assert wrote.value == nbytes.value
+    return text
+
+
+def text_format_values(vals, precision=6, unsigned=False):
+    """One value per line, as `ostream << x` prints it at the given precision (sbx_text_format_values)."""
+    dev = _check_dev(vals)
+    hd = handle_for(dev)
+    vt = _text_vt(vals, unsigned)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbx_text_format_values(
+        hd.h, vt, vals.numel(), _p(vals), precision, out, cap, C.byref(nb)))
+
+
+def text_format_coordinate(row, col, val=None, index_base=1, precision=6, lower=False, no_diagonal=False, pattern=False,
+                           unsigned=False):
+    """"<row + base> <col + base>[ <value>]\\n" per kept entry, in input order (sbx_text_format_coordinate)."""
+    dev = _check_dev(row, col, val)
+    hd = handle_for(dev)
+    vt = capi.V_NONE if val is None else _text_vt(val, unsigned)
+    flags = (capi.TEXT_LOWER if lower else 0) | (capi.TEXT_NO_DIAGONAL if no_diagonal else 0) | \
+        (capi.TEXT_PATTERN if pattern else 0)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbx_text_format_coordinate(
+        hd.h, _it(row), vt, row.numel(), _p(row), _p(col), _p(val), index_base, precision, flags, out, cap, C.byref(nb)))
+
+
+def text_format_dense(n, m, row, col, val=None, precision=6, unsigned=False):
+    """The array format of a COO: n * m value lines in column-major order, "0" where nothing is stored."""
+    dev = _check_dev(row, col, val)
+    hd = handle_for(dev)
+    vt = capi.V_NONE if val is None else _text_vt(val, unsigned)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbx_text_format_dense(
+        hd.h, _it(row), vt, n, m, row.numel(), _p(row), _p(col), _p(val), precision, out, cap, C.byref(nb)))
+
+
+def coo_symmetry_check(n, row, col, val=None, skew=False, unsigned=False):
+    """(every off-diagonal entry has a mirror that passes the value test, diagonal entries, diagonal entries != 0):
+    the symmetry check of MTXWriter::WriteCOO (sbx_coo_symmetry_check)."""
+    hd = handle_for(_check_dev(row, col, val))
+    vt = capi.V_NONE if val is None else _text_vt(val, unsigned)
+    res = (C.c_int64 * 3)()
+    hd.check(hd.lib.sbx_coo_symmetry_check(hd.h, _it(row), vt, n, row.numel(), _p(row), _p(col), _p(val), int(bool(skew)), res))
+    return bool(res[0]), res[1], res[2]
+
+
+def coo_undirected_unique_(row, col, val=None):
+    """In place: row <= col, sorted by (row, col), the first of every run of equal coordinates kept; returns the arrays
+    trimmed to what is left (sbx_coo_undirected_unique)."""
+    hd = handle_for(_check_dev(row, col, val))
+    left = C.c_int64(0)
+    hd.check(hd.lib.sbx_coo_undirected_unique(hd.h, _it(row), _vt(val), row.numel(), _p(row), _p(col), _p(val), C.byref(left)))
+    k = left.value
+    return row[:k], col[:k], (None if val is None else val[:k])
+
+
+coo_undirected_unique = coo_undirected_unique_
