@@ -29,6 +29,7 @@ def _headers_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs.append(os.path.join(ROOT, "include", "sbx.h"))
     hs.append(os.path.join(ROOT, "include", "sbx_text.h"))
+    hs.append(os.path.join(ROOT, "include", "sbx_stats.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

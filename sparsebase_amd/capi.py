@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/sbx.h and include/sbx_text.h (sparsebase_amd/lib/libsbx.so).
+"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h and include/sbx_stats.h
+(sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
 usable, loading / handle creation raises.  torch is used only as the owner of
@@ -18,6 +19,7 @@ FLAG_MOVE, FLAG_ROWS_SORTED = 1, 2
 TC_DIRECTED, TC_EXACT = 1, 2
 SB_GREEDY, SB_HUB_ORDER = 1, 2
 TEXT_LOWER, TEXT_NO_DIAGONAL, TEXT_PATTERN = 1, 2, 4
+STAT_MEDIAN, STAT_LOG = 1, 2
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -37,6 +39,12 @@ class RcmStats(C.Structure):
 
 class SlashburnStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("rounds", "hubs", "spoke_components", "initial_components", "final_gcc")]
+
+
+class StatDegrees(C.Structure):
+    _fields_ = ([(k, C.c_int64) for k in ("count", "sum", "min", "max", "zeros")] +
+                [("sumsq_lo", C.c_uint64), ("sumsq_hi", C.c_uint64), ("median_lo", C.c_int64), ("median_hi", C.c_int64),
+                 ("sum_log", C.c_double)])
 
 
 # every symbol include/sbx.h declares (tests/test_abi.py checks header <-> library <-> this table)
@@ -128,6 +136,13 @@ TEXT_PROTOTYPES = {
     "sbx_text_format_dense": ([_H, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbx_stats.h declares (tests/test_stats_abi.py checks header <-> library <-> this table): the
+# `sbx_` prefix is closed, these carry `sbxstat_`
+STATS_PROTOTYPES = {
+    "sbxstat_degree_stats": ([_H, _int, _i64, _vp, _u, C.POINTER(StatDegrees)], _int),
+    "sbxstat_csr_off_diag_block_nnz": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -139,7 +154,8 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: run `python -m sparsebase_amd.build` "
                               "(there is no CPU fallback for the HIP hot path)")
         lib = C.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()):
+        for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
+                                           list(STATS_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

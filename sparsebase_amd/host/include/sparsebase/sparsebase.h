@@ -7,10 +7,22 @@
 #include "sparsebase/converter/converter_order_one.h"
 #include "sparsebase/converter/converter_order_two.h"
 #include "sparsebase/format/array.h"
+#include "sparsebase/feature/avg_degree.h"
+#include "sparsebase/feature/avg_degree_column.h"
 #include "sparsebase/feature/bandwidth.h"
+#include "sparsebase/feature/coefficient_of_variation_degree_column.h"
 #include "sparsebase/feature/degree_distribution.h"
 #include "sparsebase/feature/degrees.h"
+#include "sparsebase/feature/geometric_avg_degree_column.h"
 #include "sparsebase/feature/jaccard_weights.h"
+#include "sparsebase/feature/max_degree.h"
+#include "sparsebase/feature/max_degree_column.h"
+#include "sparsebase/feature/median_degree_column.h"
+#include "sparsebase/feature/min_degree.h"
+#include "sparsebase/feature/min_degree_column.h"
+#include "sparsebase/feature/min_max_avg_degree.h"
+#include "sparsebase/feature/off_diag_block_nnz.h"
+#include "sparsebase/feature/standard_deviation_degree_column.h"
 #include "sparsebase/feature/triangle_count.h"
 #include "sparsebase/feature/profile.h"
 #include "sparsebase/format/coo.h"

@@ -52,6 +52,7 @@ class FeatureException : public Exception {
  public:
   FeatureException(const std::string &feature, const std::string &extractor)
       : Exception("ERROR! " + feature + " is not registered in " + extractor + "!") {}
+  explicit FeatureException(const std::string &msg) : Exception(msg) {}  // a feature that is not defined on its input
 };
 
 class FeatureParamsException : public FeatureException {

@@ -300,6 +300,33 @@ def csr_triangle_count(row_ptr, col, directed=False, exact=False):
     return out.value
 
 
+def degree_stats(ptr, median=True, log=True):
+    """Every statistic of the degrees ptr[i + 1] - ptr[i] of an offset array (a CSR's row_ptr, a CSC's col_ptr) in one
+    synchronous call: a dict of Python ints (count, sum, min, max, zeros, sumsq — one exact int —, median_lo, median_hi)
+    plus the float sum_log.  median=False leaves both medians -1, log=False leaves sum_log 0.  See
+    sbxstat_degree_stats in include/sbx_stats.h."""
+    hd = handle_for(_check_dev(ptr))
+    out = capi.StatDegrees()
+    flags = (capi.STAT_MEDIAN if median else 0) | (capi.STAT_LOG if log else 0)
+    hd.check(hd.lib.sbxstat_degree_stats(hd.h, _it(ptr), ptr.numel() - 1, _p(ptr), flags, C.byref(out)))
+    res = {k: int(getattr(out, k)) for k in ("count", "sum", "min", "max", "zeros", "median_lo", "median_hi")}
+    res["sumsq"] = (int(out.sumsq_hi) << 64) | int(out.sumsq_lo)
+    res["sum_log"] = float(out.sum_log)
+    return res
+
+
+def csr_off_diag_block_nnz(row_ptr, col, m, block_rows, block_cols=None):
+    """feature::OffDiagBlockNNZ: the number of entries outside the diagonal blocks when the rows are cut into
+    block_rows contiguous blocks and the m columns into block_cols (block_rows when None), an int.  See
+    sbxstat_csr_off_diag_block_nnz in include/sbx_stats.h for the rule."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    out = C.c_int64(0)
+    hd.check(hd.lib.sbxstat_csr_off_diag_block_nnz(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, int(m), col.numel(),
+                                                   _p(row_ptr), _p(col), int(block_rows),
+                                                   int(block_rows if block_cols is None else block_cols), C.byref(out)))
+    return out.value
+
+
 # ----------------------------------------------------------------------------- reorderers
 def degree_reorder(row_ptr, ascending=True, out=None, id_dtype=None):
     hd = handle_for(_check_dev(row_ptr))
