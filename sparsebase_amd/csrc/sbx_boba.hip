@@ -117,15 +117,8 @@ static int boba_typed(sbx_handle_t h, int64_t nodes64, int64_t nnz, const void *
   SBX_KLAUNCH(h, SBX_K_MISC, k_boba_keys, dim3(sbx_grid_for(nodes, BT, cap)), dim3(BT), ka, (const unsigned char *)seen,
               nodes, va);
   SBX_LAUNCH_CHECK(h);
-  const uint32_t *sorted_v = va;
-  if (nodes >= 2) {
-    sbx_radix_pass passes[16];
-    const int np = sbx_radix_plan(0, sbx_bits_for((uint64_t)nodes + 1), 0, 0, passes);
-    int in_b = 0;
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ka, kb, va, vb, nodes, passes, np, &in_b));
-    if (in_b) sorted_v = vb;
-  }
-  SBX_KLAUNCH(h, SBX_K_MISC, k_boba_scatter<I>, dim3(sbx_grid_for(nodes, BT, cap)), dim3(BT), sorted_v, nodes,
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &va, &vb, nodes, 0, sbx_bits_for((uint64_t)nodes + 1)));
+  SBX_KLAUNCH(h, SBX_K_MISC, k_boba_scatter<I>, dim3(sbx_grid_for(nodes, BT, cap)), dim3(BT), (const uint32_t *)va, nodes,
               (const int *)err, (I *)inv_out);
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_MISC, (int64_t)2 * sizeof(I) * nnz + (int64_t)(14 + sizeof(I)) * nodes);

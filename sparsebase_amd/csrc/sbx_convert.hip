@@ -295,25 +295,8 @@ __global__ __launch_bounds__(CV_THREADS) void k_fill_gaps(I *__restrict__ rp, co
 constexpr int EX_ITEMS = 8;
 constexpr int EX_TILE = CV_THREADS * EX_ITEMS;  // 2048 nonzeros per workgroup
 
-// first and last row of every EX_TILE-wide tile of the nonzeros, one thread per tile (large inputs: the two searches in
-// row_ptr are four dependent rounds of loads when a workgroup does them itself, and with tens of waves of workgroups
-// per CU that is most of a tile's life)
-template <typename I>
-__global__ __launch_bounds__(CV_THREADS) void k_ex_tile_spans(const I *__restrict__ rp, int64_t n, int64_t nnz,
-                                                              int64_t tiles, int2 *__restrict__ span) {
-  const int64_t t = (int64_t)blockIdx.x * CV_THREADS + threadIdx.x;
-  if (t >= tiles) return;
-  const int64_t t0 = t * EX_TILE, t1 = (t0 + EX_TILE < nnz) ? t0 + EX_TILE : nnz;
-  auto last_le = [&](int64_t v) {  // last row r with rp[r] <= v
-    int64_t lo = 0, hi = n + 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)rp[mid] > v) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
-  };
-  span[t] = make_int2((int)last_le(t0), (int)last_le(t1 - 1));
-}
+// the first and last row of every tile come from k_tile_spans on large inputs: the two searches in row_ptr are four
+// dependent rounds of loads when a workgroup does them itself
 constexpr int64_t EX_SPAN_MIN_TILES = 8192;  // from 16 M nonzeros on
 
 template <typename I, typename O, int VB, bool MOVE, bool ALIGNED16>
@@ -696,8 +679,8 @@ int launch_csr_to_coo(sbx_handle_t h, int64_t n, int64_t nnz, const O *rp, const
   int2 *span = nullptr;
   if ((int64_t)grid >= EX_SPAN_MIN_TILES) {
     SBX_TRY(sbx_salloc(h, (size_t)grid, &span));
-    SBX_KLAUNCH(h, SBX_K_CSR_TO_COO, k_ex_tile_spans<O>, dim3((grid + CV_THREADS - 1) / CV_THREADS), dim3(CV_THREADS),
-                rp, n, nnz, (int64_t)grid, span);
+    SBX_KLAUNCH(h, SBX_K_CSR_TO_COO, (k_tile_spans<O, EX_TILE, CV_THREADS>), dim3((grid + CV_THREADS - 1) / CV_THREADS),
+                dim3(CV_THREADS), rp, n, nnz, (int64_t)grid, span);
   }
   if (al)
     SBX_KLAUNCH(h, SBX_K_CSR_TO_COO, (k_csr_to_coo<I, O, VB, MOVE, true>), dim3(grid), dim3(CV_THREADS), rp, col,
@@ -883,7 +866,8 @@ int coo_to_csc_core(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, int
   // the reference's placement loop (:53-62) is a stable counting sort on the column: a stable
   // LSD radix sort over the column bits moves the records to the same places
   sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0), 0, 0, passes);
+  const int cbits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
+  const int np = sbx_radix_plan(0, cbits, 0, 0, passes);
   uint32_t *ka = nullptr, *kb = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)nnz, &ka));
   SBX_TRY(sbx_salloc(h, (size_t)nnz, &kb));
@@ -922,9 +906,9 @@ int coo_to_csc_core(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, int
     SBX_TRY(sbx_salloc(h, (size_t)nnz, &ib));
     SBX_KLAUNCH(h, SBX_K_CSC, k_csc_keys, dim3(grid), dim3(CV_THREADS), col, ka, ia, nnz);
     SBX_LAUNCH_CHECK(h);
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ka, kb, ia, ib, nnz, passes, np, &in_b));
-    SBX_KLAUNCH(h, SBX_K_CSC, k_csc_gather<8>, dim3(grid), dim3(CV_THREADS), (const uint32_t *)(in_b ? ib : ia), row,
-                val, row_out, val_out, nnz);
+    SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &ia, &ib, nnz, 0, cbits));  // (the sorted keys are in ka: in_b stays 0)
+    SBX_KLAUNCH(h, SBX_K_CSC, k_csc_gather<8>, dim3(grid), dim3(CV_THREADS), (const uint32_t *)ia, row, val, row_out,
+                val_out, nnz);
     SBX_LAUNCH_CHECK(h);
     SBX_PROF_BYTES(h, SBX_K_CSC, nnz * (int64_t)(8 + 2 * (4 + vb)));
   }
@@ -972,8 +956,6 @@ int coo_to_csc_core64(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, i
   if (nnz == 0) return sbx_fill_i64(h, col_ptr_out, 0, m + 1);
   const int vb = (val && val_out) ? sbx_value_bytes(vt) : 0;
   const unsigned grid = sbx_grid_for(nnz, CV_THREADS, 8192);
-  sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0), 0, 0, passes);
   uint64_t *ka = nullptr, *kb = nullptr;
   uint32_t *ia = nullptr, *ib = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)nnz, &ka));
@@ -982,15 +964,14 @@ int coo_to_csc_core64(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, i
   SBX_TRY(sbx_salloc(h, (size_t)nnz, &ib));
   SBX_KLAUNCH(h, SBX_K_CSC, k_csc_keys64, dim3(grid), dim3(CV_THREADS), col, ka, ia, nnz);
   SBX_LAUNCH_CHECK(h);
-  int in_b = 0;
-  if (np > 0 && nnz >= 2) SBX_TRY(sbx_radix_sort(h, 8, 4, ka, kb, ia, ib, nnz, passes, np, &in_b));
-  const uint32_t *idx = in_b ? ib : ia;
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &ia, &ib, nnz, 0, sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0)));
+  const uint32_t *idx = ia;
   if (vb == 0) SBX_KLAUNCH(h, SBX_K_CSC, k_csc_gather64<0>, dim3(grid), dim3(CV_THREADS), idx, row, val, row_out, val_out, nnz);
   else if (vb == 4) SBX_KLAUNCH(h, SBX_K_CSC, k_csc_gather64<4>, dim3(grid), dim3(CV_THREADS), idx, row, val, row_out, val_out, nnz);
   else SBX_KLAUNCH(h, SBX_K_CSC, k_csc_gather64<8>, dim3(grid), dim3(CV_THREADS), idx, row, val, row_out, val_out, nnz);
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_CSC, nnz * (int64_t)(16 + 2 * (8 + vb)));
-  SBX_TRY(sbx_coo_to_csr(h, SBX_I64, SBX_V_NONE, m, n, nnz, in_b ? kb : ka, nullptr, nullptr, col_ptr_out, nullptr, nullptr,
+  SBX_TRY(sbx_coo_to_csr(h, SBX_I64, SBX_V_NONE, m, n, nnz, ka, nullptr, nullptr, col_ptr_out, nullptr, nullptr,
                          SBX_FLAG_MOVE));
   if (rows_ascend) return SBX_OK;  // (see coo_to_csc_core)
   return sbx_csr_sort_rows(h, SBX_I64, vb ? vt : SBX_V_NONE, m, n, nnz, col_ptr_out, row_out, vb ? val_out : nullptr);

@@ -279,12 +279,9 @@ static int degree_reorder_typed(sbx_handle_t h, int64_t n, const void *row_ptr, 
     const DegreeTailEmit<P> emit = {(P *)inv_perm_out, n - top, n, ascending};
     SBX_TRY(sbx_cs::sort_emit(h, SBX_K_DEGREE, ta, ia, tb, ib, top, sbx_bits_for(hs.max_deg), emit));
   } else {  // (millions of rows of 255+ entries: the generic sort's staged stores win; then a scatter)
-    sbx_radix_pass passes[16];
-    const int np = sbx_radix_plan(0, sbx_bits_for(hs.max_deg), 0, 0, passes);
-    int in_b = 0;
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ta, tb, ia, ib, top, passes, np, &in_b));
+    SBX_TRY(sbx_sort_pairs(h, &ta, &tb, &ia, &ib, top, 0, sbx_bits_for(hs.max_deg)));
     SBX_KLAUNCH(h, SBX_K_DEGREE, k_degree_tail_emit<P>, dim3(sbx_grid_for(top, 256, 2048)), dim3(256),
-                (const uint32_t *)(in_b ? ib : ia), (P *)inv_perm_out, top, n - top, n, ascending);
+                (const uint32_t *)ia, (P *)inv_perm_out, top, n - top, n, ascending);
     SBX_LAUNCH_CHECK(h);
   }
   return SBX_OK;
@@ -345,12 +342,9 @@ static int degree_ranks_typed(sbx_handle_t h, const I *rp, int64_t n, int64_t n_
     const RankTailEmit emit = {rank, order, first};
     SBX_TRY(sbx_cs::sort_emit(h, SBX_K_RCM_MISC, ta, ia, tb, ib, n_top, sbx_bits_for(max_deg), emit));
   } else {
-    sbx_radix_pass passes[16];
-    const int np = sbx_radix_plan(0, sbx_bits_for(max_deg), 0, 0, passes);
-    int in_b = 0;
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ta, tb, ia, ib, n_top, passes, np, &in_b));
+    SBX_TRY(sbx_sort_pairs(h, &ta, &tb, &ia, &ib, n_top, 0, sbx_bits_for(max_deg)));
     SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_rank_tail_emit, dim3(sbx_grid_for(n_top, 256, 2048)), dim3(256),
-                (const uint32_t *)(in_b ? ib : ia), rank, order, n_top, first);
+                (const uint32_t *)ia, rank, order, n_top, first);
     SBX_LAUNCH_CHECK(h);
   }
   return SBX_OK;

@@ -233,3 +233,87 @@ __device__ __forceinline__ unsigned sbx_wave_append(unsigned *counter, bool want
   base = (unsigned)__builtin_amdgcn_readlane((int)base, leader);
   return base + (unsigned)__popcll(m & sbx_lanemask_lt());
 }
+
+// wave-aggregated append to a 64-bit counter (sbx_wave_append with 64-bit slots: SBX_I32_N64 takes nnz >= 2^32)
+__device__ __forceinline__ unsigned long long sbx_wave_append64(unsigned long long *counter, bool want) {
+  const uint64_t m = __ballot(want);
+  if (!m) return 0;
+  const int leader = __builtin_ctzll(m);
+  unsigned long long base = 0;
+  if (sbx_lane() == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+  base = __shfl(base, leader, 64);
+  return base + (unsigned long long)__popcll(m & sbx_lanemask_lt());
+}
+
+// ---- searches in row_ptr and tile helpers of the nonzero-parallel kernels -------------------------------------------
+// row of position p given a row r0 <= row(p) and a row r1 >= row(p): the last row r with rp[r] <= p
+template <typename N>
+__device__ __forceinline__ int64_t sbx_row_of(const N *__restrict__ rp, int64_t p, int64_t r0, int64_t r1) {
+  if ((int64_t)rp[r0 + 1] > p) return r0;  // (the common case: p in the row of the nonzero before it)
+  int64_t lo = r0 + 1, hi = r1;            // answer in [lo, hi]
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the last row r with rp[r] <= p: the row of nonzero p (over all n rows, without the shortcut)
+template <typename N>
+__device__ __forceinline__ int64_t sbx_row_of(const N *__restrict__ rp, int64_t n, int64_t p) {
+  int64_t lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// a thread's 8 consecutive columns [base, base + 8) of a tile ending at t1: two 16-byte loads where the array allows it
+// (eight 4-byte loads at a stride of 32 bytes across the lanes make eight times the requests); a slot past t1 repeats
+// the tile's last entry
+template <typename I>
+__device__ __forceinline__ void sbx_load_items8(const I *__restrict__ col, int64_t base, int64_t t1, bool vec_ok, I *c) {
+  constexpr int ITEMS = 8;  // two 16-byte loads per thread (four for 64-bit columns)
+  if (vec_ok && base + ITEMS <= t1) {
+    if (sizeof(I) == 4) {
+      const int4 a = *(const int4 *)(col + base), b = *(const int4 *)(col + base + 4);
+      c[0] = (I)a.x; c[1] = (I)a.y; c[2] = (I)a.z; c[3] = (I)a.w;
+      c[4] = (I)b.x; c[5] = (I)b.y; c[6] = (I)b.z; c[7] = (I)b.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < ITEMS; k += 2) {
+        const longlong2 a = *(const longlong2 *)(col + base + k);
+        c[k] = (I)a.x; c[k + 1] = (I)a.y;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) c[k] = col[base + k < t1 ? base + k : t1 - 1];
+  }
+}
+
+namespace {  // (a kernel in a header shared by several translation units: internal linkage)
+
+// first and last row of every TILE-wide tile of the nonzeros, one thread per tile: the two searches in row_ptr are four
+// dependent rounds of loads when a workgroup does them for itself, and 25 waves of workgroups per CU then spend half
+// their lives in them.  rp may be any ascending array of n + 1 offsets: an entry before rp[0] gets -1, one from rp[n]
+// on gets n.
+template <typename I, int TILE, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_tile_spans(const I *__restrict__ rp, int64_t n, int64_t nnz,
+                                                            int64_t tiles, int2 *__restrict__ span) {
+  const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (t >= tiles) return;
+  const int64_t t0 = t * TILE, t1 = (t0 + TILE < nnz) ? t0 + TILE : nnz;
+  auto last_le = [&](int64_t v) {  // last row r with rp[r] <= v
+    int64_t lo = 0, hi = n + 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)rp[mid] > v) hi = mid; else lo = mid + 1;
+    }
+    return lo - 1;
+  };
+  span[t] = make_int2((int)last_le(t0), (int)last_le(t1 - 1));
+}
+
+}  // namespace

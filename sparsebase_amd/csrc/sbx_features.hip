@@ -54,25 +54,6 @@ struct TileRows {
   bool head[FT_ITEMS];  // the nonzero is the first one of its row
 };
 
-// first and last row of every tile, one thread per tile: the two searches in row_ptr are four dependent rounds of
-// loads when a workgroup does them for itself, and 25 waves of workgroups per CU then spend half their lives in them
-template <typename I>
-__global__ __launch_bounds__(FT_THREADS) void k_tile_spans(const I *__restrict__ rp, int64_t n, int64_t nnz,
-                                                           int64_t tiles, int2 *__restrict__ span) {
-  const int64_t t = (int64_t)blockIdx.x * FT_THREADS + threadIdx.x;
-  if (t >= tiles) return;
-  const int64_t t0 = t * FT_TILE, t1 = (t0 + FT_TILE < nnz) ? t0 + FT_TILE : nnz;
-  auto last_le = [&](int64_t v) {  // last row r with rp[r] <= v
-    int64_t lo = 0, hi = n + 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)rp[mid] > v) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
-  };
-  span[t] = make_int2((int)last_le(t0), (int)last_le(t1 - 1));
-}
-
 template <typename I>
 __device__ __forceinline__ TileRows tile_rows(const I *__restrict__ rp, const int2 *__restrict__ span, int64_t tile,
                                               int64_t t0, int *s_head, int *s_wmax) {
@@ -106,28 +87,7 @@ __device__ __forceinline__ TileRows tile_rows(const I *__restrict__ rp, const in
   return t;
 }
 
-// this thread's FT_ITEMS consecutive columns: two 16-byte loads where the array allows it (eight 4-byte loads at a
-// stride of 32 bytes across the lanes make eight times the requests)
-template <typename I>
-__device__ __forceinline__ void load_items(const I *__restrict__ col, int64_t base, int64_t t1, bool vec_ok, I *c) {
-  static_assert(FT_ITEMS == 8, "two 16-byte loads per thread (four for 64-bit columns)");
-  if (vec_ok && base + FT_ITEMS <= t1) {
-    if (sizeof(I) == 4) {
-      const int4 a = *(const int4 *)(col + base), b = *(const int4 *)(col + base + 4);
-      c[0] = (I)a.x; c[1] = (I)a.y; c[2] = (I)a.z; c[3] = (I)a.w;
-      c[4] = (I)b.x; c[5] = (I)b.y; c[6] = (I)b.z; c[7] = (I)b.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < FT_ITEMS; k += 2) {
-        const longlong2 a = *(const longlong2 *)(col + base + k);
-        c[k] = (I)a.x; c[k + 1] = (I)a.y;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < FT_ITEMS; k++) c[k] = col[base + k < t1 ? base + k : t1 - 1];
-  }
-}
+static_assert(FT_ITEMS == 8, "sbx_load_items8 fills a thread's columns");
 
 // bandwidth.cc:100-107: max |row - col| over the nonzeros
 template <typename I, typename P>  // P: unsigned for 32-bit columns, unsigned long long for 64-bit ones
@@ -145,7 +105,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_bandwidth_csr(const I *__restric
     const int64_t t1 = (t0 + FT_TILE < nnz) ? t0 + FT_TILE : nnz;
     const int64_t base = t0 + (int64_t)tid * FT_ITEMS;
     I c[FT_ITEMS];  // in flight during the row search
-    load_items(col, base, t1, vec_ok, c);
+    sbx_load_items8(col, base, t1, vec_ok, c);
     const TileRows t = tile_rows(rp, span, tile, t0, s_head, s_wmax);
 #pragma unroll
     for (int k = 0; k < FT_ITEMS; k++) {
@@ -190,7 +150,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_profile_csr(const I *__restrict_
     const int64_t base = t0 + (int64_t)tid * FT_ITEMS;
     I c[FT_ITEMS + 1];  // c[0]: the nonzero before this thread's first one
     c[0] = base > 0 ? col[base - 1 < t1 ? base - 1 : t1 - 1] : 0;
-    load_items(col, base, t1, vec_ok, c + 1);
+    sbx_load_items8(col, base, t1, vec_ok, c + 1);
     const TileRows t = tile_rows(rp, span, tile, t0, s_head, s_wmax);
 #pragma unroll
     for (int k = 0; k < FT_ITEMS; k++) {
@@ -385,8 +345,8 @@ static int csr_bandwidth_typed(sbx_handle_t h, int64_t n, int64_t nnz, const voi
   SBX_HIP(h, hipMemsetAsync(partial, 0, grid * sizeof(P), h->stream));
   int2 *span = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)tiles, &span));
-  SBX_KLAUNCH(h, SBX_K_FEATURE, k_tile_spans<I>, dim3((unsigned)((tiles + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS),
-              (const I *)row_ptr, n, nnz, tiles, span);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tile_spans<I, FT_TILE, FT_THREADS>),
+              dim3((unsigned)((tiles + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS), (const I *)row_ptr, n, nnz, tiles, span);
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_bandwidth_csr<I, P>), dim3((unsigned)tiles), dim3(FT_THREADS), (const I *)row_ptr,
               (const I *)col, n, nnz, partial, ((uintptr_t)col & 15) == 0, (const int2 *)span);
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_feature_finish<P>, dim3(1), dim3(FT_THREADS), (const P *)partial,
@@ -434,8 +394,9 @@ static int csr_profile_typed(sbx_handle_t h, int64_t n, int64_t nnz, const void 
     SBX_HIP(h, hipMemsetAsync(psum, 0, (grid + 3) * sizeof(unsigned long long), h->stream));
     int2 *span = nullptr;
     SBX_TRY(sbx_salloc(h, (size_t)tiles, &span));
-    SBX_KLAUNCH(h, SBX_K_FEATURE, k_tile_spans<I>, dim3((unsigned)((tiles + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS),
-                (const I *)row_ptr, n, nnz, tiles, span);
+    SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tile_spans<I, FT_TILE, FT_THREADS>),
+                dim3((unsigned)((tiles + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS), (const I *)row_ptr, n, nnz, tiles,
+                span);
     SBX_KLAUNCH(h, SBX_K_FEATURE, k_profile_csr<I>, dim3((unsigned)tiles), dim3(FT_THREADS), (const I *)row_ptr,
                 (const I *)col, n, nnz, psum, (int *)(res + 2), ((uintptr_t)col & 15) == 0, (const int2 *)span);
     SBX_KLAUNCH(h, SBX_K_FEATURE, k_feature_finish<unsigned>, dim3(1), dim3(FT_THREADS), (const unsigned *)nullptr,

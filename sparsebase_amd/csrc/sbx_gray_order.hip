@@ -248,18 +248,11 @@ int gray_order_typed(sbx_handle_t h, int64_t n, int64_t nnz, const I *deg, const
   SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &rank));
   SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &section));
   SBX_HIP(h, hipMemsetAsync(present, 0, sizeof(uint32_t) * (size_t)(dmax + 2), h->stream));
-  sbx_radix_pass passes[16];
-  int in_b = 0;
   // 1: by degree (sparse rows; stable: ids ascending inside a degree)
   SBX_KLAUNCH(h, SBX_K_GRAY, k_go_degree_keys<I>, dim3(grid), dim3(256), deg, n, thr, ka, ia, present);
   SBX_LAUNCH_CHECK(h);
   uint32_t *id = ia, *id_tmp = ib;
-  const int dbits = sbx_bits_for((uint64_t)dmax);
-  if (dbits > 0) {
-    const int np = sbx_radix_plan(0, dbits, 0, 0, passes);
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ka, kb, ia, ib, n, passes, np, &in_b));
-    if (in_b) id = ib, id_tmp = ia;
-  }
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)dmax)));
   // the sections of the degrees
   uint32_t n_present = 0, *tot = nullptr;
   SBX_TRY(sbx_salloc(h, 1, &tot));
@@ -274,20 +267,14 @@ int gray_order_typed(sbx_handle_t h, int64_t n, int64_t nnz, const I *deg, const
     SBX_KLAUNCH(h, SBX_K_GRAY, k_go_signed_keys<I>, dim3(grid), dim3(256), (const uint32_t *)id, deg, gkey, n, thr,
                 (const uint32_t *)section, sparse_banded ? 1 : 0, dense_banded ? 1 : 0, mask, qa);
     SBX_LAUNCH_CHECK(h);
-    const int np = sbx_radix_plan(0, bits, 0, 0, passes);
-    SBX_TRY(sbx_radix_sort(h, 8, 4, qa, qb, id, id_tmp, n, passes, np, &in_b));
-    if (in_b) { uint32_t *t = id; id = id_tmp; id_tmp = t; }
+    SBX_TRY(sbx_sort_pairs(h, &qa, &qb, &id, &id_tmp, n, 0, bits));
   }
   // 3: by (class, section)
   const uint32_t dense_class = n_sections + 1u;
   SBX_KLAUNCH(h, SBX_K_GRAY, k_go_class_keys<I>, dim3(grid), dim3(256), (const uint32_t *)id, deg, n, thr,
               (const uint32_t *)section, sparse_banded ? 1 : 0, dense_class, ka);
   SBX_LAUNCH_CHECK(h);
-  {
-    const int np = sbx_radix_plan(0, sbx_bits_for((uint64_t)dense_class), 0, 0, passes);
-    SBX_TRY(sbx_radix_sort(h, 4, 4, ka, kb, id, id_tmp, n, passes, np, &in_b));
-    if (in_b) { uint32_t *t = id; id = id_tmp; id_tmp = t; }
-  }
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)dense_class)));
   SBX_KLAUNCH(h, SBX_K_GRAY, k_go_emit<I>, dim3(grid), dim3(256), (const uint32_t *)id, n, inv_out);
   SBX_LAUNCH_CHECK(h);
   return SBX_OK;

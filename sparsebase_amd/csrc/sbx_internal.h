@@ -281,6 +281,23 @@ int sbx_radix_sort(sbx_handle_t h, int key_bytes, int payload_bytes, void *keys_
                    void *vals_a, void *vals_b, int64_t count, const sbx_radix_pass *passes,
                    int num_passes, int *result_in_b);
 
+// The same sort over the key bits [lo0,hi0) u [lo1,hi1) of ping-pong buffers: on return *keys_a / *vals_a hold the
+// sorted records and *keys_b / *vals_b the other buffers (vals_a = vals_b = nullptr without a payload).  With
+// count < 2 or no bit to sort by it returns at once and touches nothing.
+int sbx_sort_pairs(sbx_handle_t h, int key_bytes, int payload_bytes, void **keys_a, void **keys_b, void **vals_a,
+                   void **vals_b, int64_t count, int lo0, int hi0, int lo1, int hi1);
+// (typed fronts: the record sizes come from the buffers' own types)
+template <typename K, typename V>
+inline int sbx_sort_pairs(sbx_handle_t h, K **ka, K **kb, V **va, V **vb, int64_t count, int lo0, int hi0, int lo1 = 0,
+                          int hi1 = 0) {
+  return sbx_sort_pairs(h, (int)sizeof(K), (int)sizeof(V), (void **)ka, (void **)kb, (void **)va, (void **)vb, count, lo0,
+                        hi0, lo1, hi1);
+}
+template <typename K>
+inline int sbx_sort_keys(sbx_handle_t h, K **ka, K **kb, int64_t count, int lo0, int hi0, int lo1 = 0, int hi1 = 0) {
+  return sbx_sort_pairs(h, (int)sizeof(K), 0, (void **)ka, (void **)kb, nullptr, nullptr, count, lo0, hi0, lo1, hi1);
+}
+
 // The same sort reading its records from, and leaving them in, the caller's own arrays: the first pass loads from
 // `src`, the last one stores to `dst` (which may be the arrays of `src`: needs num_passes >= 2), the passes between
 // use (keys_a, vals_a) / (keys_b, vals_b) — no pack kernel before and no unpack kernel behind the sort.  A side is

@@ -56,37 +56,14 @@ __device__ __forceinline__ int64_t jac_bst(const T *row, int64_t len, I target) 
 template <typename F>
 __device__ __forceinline__ bool jac_is_nan(F x) { return x != x; }
 
-// wave-aggregated append to a 64-bit counter (sbx_wave_append with 64-bit slots: SBX_I32_N64 takes nnz >= 2^32)
-__device__ __forceinline__ unsigned long long jac_append(unsigned long long *counter, bool want) {
-  const uint64_t m = __ballot(want);
-  if (!m) return 0;
-  const int leader = __builtin_ctzll(m);
-  unsigned long long base = 0;
-  if (sbx_lane() == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-  base = __shfl(base, leader, 64);
-  return base + (unsigned long long)__popcll(m & sbx_lanemask_lt());
-}
-
-// row of position p given a row r0 <= row(p) and a row r1 >= row(p): the last row r with rp[r] <= p
-template <typename N>
-__device__ __forceinline__ int64_t jac_row_of(const N *__restrict__ rp, int64_t p, int64_t r0, int64_t r1) {
-  if ((int64_t)rp[r0 + 1] > p) return r0;  // (the common case: p in the row of the nonzero before it)
-  int64_t lo = r0 + 1, hi = r1;            // answer in [lo, hi]
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // rows of a thread's JITEMS consecutive positions [p0, p0 + k): two searches over all rows, then narrow ones
 template <typename N>
 __device__ __forceinline__ void jac_rows(const N *__restrict__ rp, int64_t n, int64_t p0, int k, int64_t *row) {
-  row[0] = jac_row_of(rp, p0, 0, n - 1);
-  const int64_t r_last = jac_row_of(rp, p0 + k - 1, row[0], n - 1);
+  row[0] = sbx_row_of(rp, p0, 0, n - 1);
+  const int64_t r_last = sbx_row_of(rp, p0 + k - 1, row[0], n - 1);
 #pragma unroll
   for (int j = 1; j < JITEMS; j++)
-    if (j < k) row[j] = jac_row_of(rp, p0 + j, row[j - 1], r_last);
+    if (j < k) row[j] = sbx_row_of(rp, p0 + j, row[j - 1], r_last);
 }
 
 __global__ __launch_bounds__(JT) void k_jac_fill_f32(uint32_t *__restrict__ out, int64_t count) {
@@ -168,7 +145,7 @@ __global__ __launch_bounds__(JT) void k_jac_scatter(const N *__restrict__ rp, in
 #pragma unroll
       for (int b = 0; b < JB_COUNT; b++) {
         const bool want = c[j] == b;
-        const unsigned long long slot = jac_append(&ctr[JC_CUR + b], want);
+        const unsigned long long slot = sbx_wave_append64(&ctr[JC_CUR + b], want);
         if (want) {
           epos[base[b] + slot] = (N)(p0 + j);
           erow[base[b] + slot] = (I)row[j];

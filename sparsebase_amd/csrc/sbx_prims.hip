@@ -12,6 +12,8 @@
 // Traffic per pass: one read + one write of (key, payload).
 #include <stdlib.h>
 
+#include <utility>
+
 #include "sbx_device.h"
 #include "sbx_internal.h"
 
@@ -761,4 +763,19 @@ int sbx_radix_sort(sbx_handle_t h, int key_bytes, int payload_bytes, void *keys_
                                                           num_passes, result_in_b);
   }
   SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "radix sort: key_bytes=%d payload_bytes=%d", key_bytes, payload_bytes);
+}
+
+int sbx_sort_pairs(sbx_handle_t h, int key_bytes, int payload_bytes, void **keys_a, void **keys_b, void **vals_a,
+                   void **vals_b, int64_t count, int lo0, int hi0, int lo1, int hi1) {
+  sbx_radix_pass passes[16];
+  const int np = sbx_radix_plan(lo0, hi0, lo1, hi1, passes);
+  if (count < 2 || np == 0) return SBX_OK;
+  int in_b = 0;
+  SBX_TRY(sbx_radix_sort(h, key_bytes, payload_bytes, *keys_a, *keys_b, payload_bytes ? *vals_a : nullptr,
+                         payload_bytes ? *vals_b : nullptr, count, passes, np, &in_b));
+  if (in_b) {
+    std::swap(*keys_a, *keys_b);
+    if (payload_bytes) std::swap(*vals_a, *vals_b);
+  }
+  return SBX_OK;
 }

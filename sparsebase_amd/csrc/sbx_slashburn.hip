@@ -19,7 +19,6 @@
 // Scratch comes from the handle's arena.  Read-backs per call: the column check, the phase-0 component count, and per
 // round the component count plus one per wide BFS level and one per run of narrow levels.
 #include <cstddef>
-#include <utility>
 
 #include "sbx_device.h"
 #include "sbx_internal.h"
@@ -60,17 +59,6 @@ __device__ __forceinline__ unsigned long long sb_ld64(const unsigned long long *
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the last row r with rp[r] <= p: the row of nonzero p
-template <typename N>
-__device__ __forceinline__ int64_t sb_row_of(const N *__restrict__ rp, int64_t n, int64_t p) {
-  int64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 #define SB_GRID_LOOP(i, count) \
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)(count); i += (int64_t)gridDim.x * blockDim.x)
 
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(ST) void k_sb_tkeys(const N *__restrict__ rp, const
       dv->bad = 1;
       tkey[p] = 0;
     } else {
-      tkey[p] = (uint64_t)c << 32 | (uint64_t)sb_row_of(rp, n, p);
+      tkey[p] = (uint64_t)c << 32 | (uint64_t)sbx_row_of(rp, n, p);
     }
   }
 }
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(ST) void k_sb_emit_stored(const N *__restrict__ rp,
                                                        int64_t nnz, const uint32_t *__restrict__ srp,
                                                        uint32_t *__restrict__ scol) {
   SB_GRID_LOOP(p, nnz) {
-    const int64_t r = sb_row_of(rp, n, p);
+    const int64_t r = sbx_row_of(rp, n, p);
     scol[srp[r] + (uint32_t)(p - (int64_t)rp[r])] = (uint32_t)col[p];
   }
 }
@@ -687,34 +675,6 @@ static unsigned sb_grid(const SbCall &c, int64_t items, int per_block = ST) {
   return sbx_grid_for(items, per_block, (int64_t)c.h->num_cus * 32);
 }
 
-static int sb_sort32(SbCall &c, uint32_t **ka, uint32_t **kb, uint32_t **va, uint32_t **vb, int64_t cnt, int bits) {
-  if (cnt < 2 || bits == 0) return SBX_OK;
-  sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, bits, 0, 0, passes);
-  int in_b = 0;
-  SBX_TRY(sbx_radix_sort(c.h, 4, 4, *ka, *kb, *va, *vb, cnt, passes, np, &in_b));
-  if (in_b) {
-    std::swap(*ka, *kb);
-    std::swap(*va, *vb);
-  }
-  return SBX_OK;
-}
-
-// 64-bit keys with significant bits [0, lo_bits) u [32, 32 + hi_bits); optional 4-byte payload
-static int sb_sort64(SbCall &c, uint64_t **ka, uint64_t **kb, uint32_t **va, uint32_t **vb, int64_t cnt, int lo_bits,
-                     int hi_bits) {
-  if (cnt < 2 || lo_bits + hi_bits == 0) return SBX_OK;
-  sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, lo_bits, 32, 32 + hi_bits, passes);
-  int in_b = 0;
-  SBX_TRY(sbx_radix_sort(c.h, 8, va ? 4 : 0, *ka, *kb, va ? *va : nullptr, vb ? *vb : nullptr, cnt, passes, np, &in_b));
-  if (in_b) {
-    std::swap(*ka, *kb);
-    if (va) std::swap(*va, *vb);
-  }
-  return SBX_OK;
-}
-
 // components of S over inE: parent[] becomes the label; returns (count, packed GCC) through one read-back
 static int sb_components(SbCall &c, int phase0, unsigned *ncomp, unsigned long long *gcc, unsigned *noroot) {
   sbx_handle_t h = c.h;
@@ -758,7 +718,7 @@ static int sb_place_components(SbCall &c, int phase0, unsigned ncomp, unsigned n
   SBX_KLAUNCH(h, SBX_K_MISC, k_sb_comp_keys1, dim3(sb_grid(c, ncomp)), dim3(ST), (const uint32_t *)list, (int64_t)ncomp,
               phase0, (const unsigned long long *)c.rkey, ka, va);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sb_sort32(c, &ka, &kb, &va, &vb, ncomp, sbx_bits_for((uint64_t)(c.n - 1))));
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &va, &vb, ncomp, 0, sbx_bits_for((uint64_t)(c.n - 1))));
   // sort 2: stable by (hub index?, size)
   const int size_bits = sbx_bits_for((uint64_t)e_size);
   const int hub_bits = (!phase0 && c.hub_order) ? sbx_bits_for((uint64_t)(c.k - 1)) : 0;
@@ -768,7 +728,7 @@ static int sb_place_components(SbCall &c, int phase0, unsigned ncomp, unsigned n
               phase0, (int)c.hub_order, (const unsigned long long *)c.rkey, (const uint32_t *)c.csize,
               (const uint32_t *)c.hoff, c.k, gcc, gcc_key, k64a);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sb_sort64(c, &k64a, &k64b, &va, &vb, ncomp, size_bits, hub_bits));
+  SBX_TRY(sbx_sort_pairs(h, &k64a, &k64b, &va, &vb, ncomp, 0, size_bits, 32, 32 + hub_bits));
   const uint32_t *comp = va;
   SBX_KLAUNCH(h, SBX_K_MISC, k_sb_level0, dim3(sb_grid(c, nplace)), dim3(ST), comp, (int64_t)nplace, phase0,
               (const unsigned long long *)c.rkey, c.cidx, c.inE, c.fr, c.seq, c.dv);
@@ -803,7 +763,7 @@ static int sb_place_components(SbCall &c, int phase0, unsigned ncomp, unsigned n
     SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_sb_bfs_gather, dim3(sb_grid(c, cnt)), dim3(ST), (const uint32_t *)c.nxt, cnt,
                 (const unsigned long long *)c.key, ka64, pa);
     SBX_LAUNCH_CHECK(h);
-    SBX_TRY(sb_sort64(c, &ka64, &kb64, &pa, &pb, cnt, idx_bits, sbx_bits_for((uint64_t)(f - 1))));
+    SBX_TRY(sbx_sort_pairs(h, &ka64, &kb64, &pa, &pb, cnt, 0, idx_bits, 32, 32 + sbx_bits_for((uint64_t)(f - 1))));
     SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_sb_bfs_commit, dim3(sb_grid(c, cnt)), dim3(ST), (const uint32_t *)pa, cnt,
                 (uint32_t)off, c.inE, c.fr, c.seq, c.dv);
     SBX_LAUNCH_CHECK(h);
@@ -817,7 +777,7 @@ static int sb_place_components(SbCall &c, int phase0, unsigned ncomp, unsigned n
   SBX_KLAUNCH(h, SBX_K_MISC, k_sb_seq_keys, dim3(sb_grid(c, off)), dim3(ST), (const uint32_t *)c.seq, off,
               (const uint32_t *)c.parent, (const uint32_t *)c.cidx, ka2, va2);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sb_sort32(c, &ka2, &kb2, &va2, &vb2, off, sbx_bits_for((uint64_t)(nplace - 1))));
+  SBX_TRY(sbx_sort_pairs(h, &ka2, &kb2, &va2, &vb2, off, 0, sbx_bits_for((uint64_t)(nplace - 1))));
   const uint32_t top = (uint32_t)(c.n - 1 - c.placed_back);
   SBX_KLAUNCH(h, SBX_K_MISC, k_sb_place, dim3(sb_grid(c, off)), dim3(ST), (const uint32_t *)va2, off, top, c.pos);
   SBX_LAUNCH_CHECK(h);
@@ -837,8 +797,8 @@ static int sb_hubs(SbCall &c, int64_t e_size, uint32_t base) {
     SBX_KLAUNCH(h, SBX_K_DEGREE, k_sb_greedy_keys, dim3(gn), dim3(ST), (const unsigned char *)c.inE,
                 (const uint32_t *)c.deg, c.n, c.maxdeg, ka);
     SBX_LAUNCH_CHECK(h);
-    SBX_TRY(sb_sort64(c, &ka, &kb, nullptr, nullptr, c.n, sbx_bits_for((uint64_t)(c.n - 1)),
-                      sbx_bits_for((uint64_t)c.maxdeg + 1)));
+    SBX_TRY(sbx_sort_keys(h, &ka, &kb, c.n, 0, sbx_bits_for((uint64_t)(c.n - 1)), 32,
+                          32 + sbx_bits_for((uint64_t)c.maxdeg + 1)));
     SBX_KLAUNCH(h, SBX_K_DEGREE, k_sb_greedy, dim3(1), dim3(SB_WG), (const uint32_t *)c.srp, (const uint32_t *)c.scol,
                 c.inE, (const uint64_t *)ka, e_size, c.maxdeg, c.k, c.cur, c.hub);
     SBX_LAUNCH_CHECK(h);
@@ -863,8 +823,8 @@ static int sb_hubs(SbCall &c, int64_t e_size, uint32_t base) {
                 (const uint32_t *)c.deg, c.n, c.k, (const int64_t *)c.x, c.dv, c.hkey);
     SBX_LAUNCH_CHECK(h);
     uint64_t *ka = c.hkey, *kb = c.hkey_b;
-    SBX_TRY(sb_sort64(c, &ka, &kb, nullptr, nullptr, c.k, sbx_bits_for((uint64_t)(c.n - 1)),
-                      sbx_bits_for((uint64_t)c.maxdeg)));
+    SBX_TRY(sbx_sort_keys(h, &ka, &kb, c.k, 0, sbx_bits_for((uint64_t)(c.n - 1)), 32,
+                          32 + sbx_bits_for((uint64_t)c.maxdeg)));
     SBX_KLAUNCH(h, SBX_K_DEGREE, k_sb_hub_commit, dim3(sb_grid(c, c.k)), dim3(ST), (const uint64_t *)ka, c.hub, c.k,
                 c.n, base, (const uint32_t *)c.srp, c.inE, c.pos, c.hlen);
   }
@@ -903,8 +863,8 @@ static int sb_typed(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr,
     unsigned bad = 0;
     SBX_TRY(sbx_readback(h, &bad, &c.dv->bad, sizeof(bad)));
     if (bad) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbx_slashburn_reorder: a column lies outside [0, n)");
-    SBX_TRY(sb_sort64(c, &tkey, &ttmp, nullptr, nullptr, nnz, sbx_bits_for((uint64_t)(n - 1)),
-                      sbx_bits_for((uint64_t)(n - 1))));
+    SBX_TRY(sbx_sort_keys(h, &tkey, &ttmp, nnz, 0, sbx_bits_for((uint64_t)(n - 1)), 32,
+                          32 + sbx_bits_for((uint64_t)(n - 1))));
     SBX_KLAUNCH(h, SBX_K_CSC, k_sb_offsets, dim3(gn1), dim3(ST), (const uint64_t *)tkey, nnz, n, tptr);
     SBX_KLAUNCH(h, SBX_K_CSC, k_sb_keep, dim3(gz), dim3(ST), (const uint64_t *)tkey, nnz, (const uint32_t *)tptr, kscan);
     SBX_LAUNCH_CHECK(h);

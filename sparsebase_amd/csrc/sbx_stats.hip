@@ -365,43 +365,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_od_bounds(const O *__restrict__ 
   pos[p] = v < nnz ? v : nnz;
 }
 
-// the block of every tile's first and last entry, one thread per tile: -1 before pos[0], `blocks` from pos[blocks] on
-__global__ __launch_bounds__(OD_THREADS) void k_od_spans(const int64_t *__restrict__ pos, int64_t blocks, int64_t nnz,
-                                                         int64_t tiles, int2 *__restrict__ span) {
-  const int64_t t = (int64_t)blockIdx.x * OD_THREADS + threadIdx.x;
-  if (t >= tiles) return;
-  const int64_t t0 = t * OD_TILE, t1 = (t0 + OD_TILE < nnz) ? t0 + OD_TILE : nnz;
-  auto last_le = [&](int64_t v) {  // last p in [0, blocks] with pos[p] <= v, or -1
-    int64_t lo = 0, hi = blocks + 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (pos[mid] > v) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
-  };
-  span[t] = make_int2((int)last_le(t0), (int)last_le(t1 - 1));
-}
-
-template <typename C>
-__device__ __forceinline__ void load_cols(const C *__restrict__ col, int64_t base, int64_t t1, bool vec_ok, C *c) {
-  static_assert(OD_ITEMS == 8, "two 16-byte loads per thread (four for 64-bit columns)");
-  if (vec_ok && base + OD_ITEMS <= t1) {
-    if (sizeof(C) == 4) {
-      const int4 a = *(const int4 *)(col + base), b = *(const int4 *)(col + base + 4);
-      c[0] = (C)a.x; c[1] = (C)a.y; c[2] = (C)a.z; c[3] = (C)a.w;
-      c[4] = (C)b.x; c[5] = (C)b.y; c[6] = (C)b.z; c[7] = (C)b.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < OD_ITEMS; k += 2) {
-        const longlong2 a = *(const longlong2 *)(col + base + k);
-        c[k] = (C)a.x; c[k + 1] = (C)a.y;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < OD_ITEMS; k++) c[k] = col[base + k < t1 ? base + k : t1 - 1];
-  }
-}
+static_assert(OD_ITEMS == 8, "sbx_load_items8 fills a thread's columns");
 
 struct OdRange {
   int64_t cs, ce;
@@ -439,7 +403,7 @@ __global__ __launch_bounds__(OD_THREADS) void k_od_count(const C *__restrict__ c
     const int64_t base = t0 + (int64_t)tid * OD_ITEMS;
     if (base >= t1) continue;
     C c[OD_ITEMS];
-    load_cols(col, base, t1, vec_ok, c);
+    sbx_load_items8(col, base, t1, vec_ok, c);
     const int2 sp = span[tile];
     // the block of this thread's first entry: searched among the tile's blocks only (none to search in most tiles)
     int64_t lo = sp.x, hi = sp.y;
@@ -503,8 +467,10 @@ int off_diag_typed(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
   SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &partial));
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_od_bounds<O>, dim3((unsigned)((blocks + 1 + OD_THREADS - 1) / OD_THREADS)), dim3(OD_THREADS),
               (const O *)row_ptr, n, bh, blocks, nnz, pos);
-  SBX_KLAUNCH(h, SBX_K_FEATURE, k_od_spans, dim3((unsigned)((tiles + OD_THREADS - 1) / OD_THREADS)), dim3(OD_THREADS),
-              (const int64_t *)pos, blocks, nnz, tiles, span);
+  // the block of every tile's first and last entry: -1 before pos[0], `blocks` from pos[blocks] on
+  SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tile_spans<int64_t, OD_TILE, OD_THREADS>),
+              dim3((unsigned)((tiles + OD_THREADS - 1) / OD_THREADS)), dim3(OD_THREADS), (const int64_t *)pos, blocks, nnz, tiles,
+              span);
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_od_count<C>, dim3(grid), dim3(OD_THREADS), (const C *)col, nnz, tiles, (const int64_t *)pos,
               (const int2 *)span, blocks, m, bw, ((uintptr_t)col & 15) == 0, partial);
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_od_finish, dim3(1), dim3(OD_THREADS), (const unsigned long long *)partial, (int)grid,

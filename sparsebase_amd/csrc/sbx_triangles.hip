@@ -40,18 +40,6 @@ constexpr int TC_SUM = 0, TC_CNT = 1, TC_CUR = 5, TC_WORDS = 9;
 __device__ __forceinline__ uint32_t tc_hi(uint64_t k) { return (uint32_t)(k >> 32); }
 __device__ __forceinline__ uint32_t tc_lo(uint64_t k) { return (uint32_t)k; }
 
-// the last row r in [r0, r1] with rp[r] <= p (rp[r0] <= p)
-template <typename N>
-__device__ __forceinline__ int64_t tc_row_of(const N *__restrict__ rp, int64_t p, int64_t r0, int64_t r1) {
-  if ((int64_t)rp[r0 + 1] > p) return r0;  // (the common case: p in the row of the nonzero before it)
-  int64_t lo = r0 + 1, hi = r1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // f(p, row of p) for every nonzero p, TITEMS consecutive ones per thread: two searches over all rows, then narrow
 // ones.  No cross-lane operation may sit in f: the trip count differs between lanes.
 template <typename N, typename F>
@@ -59,13 +47,13 @@ __device__ __forceinline__ void tc_nonzeros(const N *__restrict__ rp, int64_t n,
   const int64_t stride = (int64_t)gridDim.x * TT * TITEMS;
   for (int64_t p0 = ((int64_t)blockIdx.x * TT + threadIdx.x) * TITEMS; p0 < nnz; p0 += stride) {
     const int k = nnz - p0 < TITEMS ? (int)(nnz - p0) : TITEMS;
-    int64_t r = tc_row_of(rp, p0, 0, n - 1);
-    const int64_t r_last = tc_row_of(rp, p0 + k - 1, r, n - 1);
+    int64_t r = sbx_row_of(rp, p0, 0, n - 1);
+    const int64_t r_last = sbx_row_of(rp, p0 + k - 1, r, n - 1);
     f(p0, r);
 #pragma unroll
     for (int j = 1; j < TITEMS; j++)
       if (j < k) {
-        r = tc_row_of(rp, p0 + j, r, r_last);
+        r = sbx_row_of(rp, p0 + j, r, r_last);
         f(p0 + j, r);
       }
   }
@@ -103,17 +91,6 @@ __device__ __forceinline__ uint32_t tc_count_le(const uint64_t *__restrict__ k, 
 __device__ __forceinline__ void tc_add_sum(unsigned long long *sum, unsigned long long acc) {
   acc = sbx_wave_sum(acc);
   if (sbx_lane() == 0 && acc) atomicAdd(sum, acc);
-}
-
-// wave-aggregated append to a 64-bit counter
-__device__ __forceinline__ unsigned long long tc_append(unsigned long long *counter, bool want) {
-  const uint64_t m = __ballot(want);
-  if (!m) return 0;
-  const int leader = __builtin_ctzll(m);
-  unsigned long long base = 0;
-  if (sbx_lane() == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-  base = __shfl(base, leader, 64);
-  return base + (unsigned long long)__popcll(m & sbx_lanemask_lt());
 }
 
 // ---- reference mode -------------------------------------------------------------------------------------------------
@@ -331,7 +308,7 @@ __global__ __launch_bounds__(TT) void k_tc_scatter(const unsigned char *__restri
 #pragma unroll
     for (int b = 0; b < TB_COUNT; b++) {
       const bool want = c == b;
-      const unsigned long long slot = tc_append(&ctr[TC_CUR + b], want);
+      const unsigned long long slot = sbx_wave_append64(&ctr[TC_CUR + b], want);
       if (want) idx[base[b] + slot] = (uint32_t)i;
     }
   }
@@ -389,21 +366,6 @@ __global__ __launch_bounds__(TT) void k_tc_block(const uint64_t *__restrict__ it
     if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
   } while (0)
 
-// radix sort of cnt keys whose two fields hold values <= n (hi) and < n (lo); *keys / *tmp swap when the result
-// lands in the temporary
-static int tc_sort(sbx_handle_t h, int64_t n, int64_t cnt, uint64_t **keys, uint64_t **tmp) {
-  sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, sbx_bits_for((uint64_t)(n - 1)), 32, 32 + sbx_bits_for((uint64_t)n), passes);
-  int in_b = 0;
-  SBX_TRY(sbx_radix_sort(h, 8, 0, *keys, *tmp, nullptr, nullptr, cnt, passes, np, &in_b));
-  if (in_b) {
-    uint64_t *t = *keys;
-    *keys = *tmp;
-    *tmp = t;
-  }
-  return SBX_OK;
-}
-
 static int tc_offsets(sbx_handle_t h, const uint64_t *keys, int64_t cnt_host, const uint32_t *cnt_dev, int64_t n,
                       uint32_t *off) {
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_tc_offsets, dim3(sbx_grid_for(n + 1, TT, (int64_t)h->num_cus * 32)), dim3(TT), keys,
@@ -456,6 +418,8 @@ static int tc_intersect(sbx_handle_t h, const uint64_t *items, int64_t cap, cons
 template <typename I, typename N, bool DIRECTED>
 static int tc_reference(sbx_handle_t h, int64_t n, int64_t nnz, const N *rp, const I *col, unsigned long long *ctr) {
   const unsigned g_nz = sbx_grid_for((nnz + TITEMS - 1) / TITEMS, TT, (int64_t)h->num_cus * 64);
+  // (the sorts' bit ranges: a key's low field holds a value < n, its high field a row <= n)
+  const int lo_bits = sbx_bits_for((uint64_t)(n - 1)), hi_end = 32 + sbx_bits_for((uint64_t)n);
   uint32_t *first = nullptr, *offa = nullptr, *offb = nullptr;
   uint64_t *ka = nullptr, *kb = nullptr, *tmp = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)n, &first));
@@ -471,10 +435,10 @@ static int tc_reference(sbx_handle_t h, int64_t n, int64_t nnz, const N *rp, con
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tc_ref_keys<I, N, DIRECTED>), dim3(g_nz), dim3(TT), rp, col, n, nnz,
               (const uint32_t *)first, ka, kb);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(tc_sort(h, n, nnz, &ka, &tmp));
+  SBX_TRY(sbx_sort_keys(h, &ka, &tmp, nnz, 0, lo_bits, 32, hi_end));
   SBX_TRY(tc_offsets(h, ka, nnz, nullptr, n, offa));
   if (DIRECTED) {
-    SBX_TRY(tc_sort(h, n, nnz, &kb, &tmp));
+    SBX_TRY(sbx_sort_keys(h, &kb, &tmp, nnz, 0, lo_bits, 32, hi_end));
     SBX_TRY(tc_offsets(h, kb, nnz, nullptr, n, offb));
   }
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tc_ref_count<I, N, DIRECTED>), dim3(g_nz), dim3(TT), rp, col, n, nnz,
@@ -489,6 +453,8 @@ static int tc_exact_undirected(sbx_handle_t h, int64_t n, int64_t nnz, const N *
                                unsigned long long *ctr) {
   const int64_t cap = 2 * nnz;  // < 2^32: nnz < 2^31
   const unsigned g_nz = sbx_grid_for((nnz + TITEMS - 1) / TITEMS, TT, (int64_t)h->num_cus * 64);
+  // (the sorts' bit ranges: a key's low field holds a value < n, its high field a row <= n)
+  const int lo_bits = sbx_bits_for((uint64_t)(n - 1)), hi_end = 32 + sbx_bits_for((uint64_t)n);
   uint64_t *ka = nullptr, *tmp = nullptr, *sym = nullptr;
   uint32_t *flag = nullptr, *adj = nullptr, *off = nullptr, *oadj = nullptr, *ooff = nullptr, *m_dev = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)cap, &ka));
@@ -502,7 +468,7 @@ static int tc_exact_undirected(sbx_handle_t h, int64_t n, int64_t nnz, const N *
   SBX_TRY(sbx_salloc(h, 2, &m_dev));
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tc_emit<I, N, false>), dim3(g_nz), dim3(TT), rp, col, n, nnz, ka, (uint64_t *)nullptr);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(tc_sort(h, n, cap, &ka, &tmp));
+  SBX_TRY(sbx_sort_keys(h, &ka, &tmp, cap, 0, lo_bits, 32, hi_end));
   SBX_TRY(tc_unique(h, n, ka, cap, flag, sym, adj, off, m_dev));
   // orientation: the oriented keys go to the sort's input buffer, free again
   const unsigned g = sbx_grid_for(cap, TT, (int64_t)h->num_cus * 32);
@@ -521,6 +487,8 @@ template <typename I, typename N>
 static int tc_exact_directed(sbx_handle_t h, int64_t n, int64_t nnz, const N *rp, const I *col,
                              unsigned long long *ctr) {
   const unsigned g_nz = sbx_grid_for((nnz + TITEMS - 1) / TITEMS, TT, (int64_t)h->num_cus * 64);
+  // (the sorts' bit ranges: a key's low field holds a value < n, its high field a row <= n)
+  const int lo_bits = sbx_bits_for((uint64_t)(n - 1)), hi_end = 32 + sbx_bits_for((uint64_t)n);
   uint64_t *kout = nullptr, *kin = nullptr, *tmp = nullptr, *uout = nullptr, *uin = nullptr;
   uint32_t *flag = nullptr, *out_adj = nullptr, *in_adj = nullptr, *out_off = nullptr, *in_off = nullptr, *m_dev = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)nnz, &kout));
@@ -536,9 +504,9 @@ static int tc_exact_directed(sbx_handle_t h, int64_t n, int64_t nnz, const N *rp
   SBX_TRY(sbx_salloc(h, 2, &m_dev));
   SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tc_emit<I, N, true>), dim3(g_nz), dim3(TT), rp, col, n, nnz, kout, kin);
   SBX_LAUNCH_CHECK(h);
-  SBX_TRY(tc_sort(h, n, nnz, &kout, &tmp));
+  SBX_TRY(sbx_sort_keys(h, &kout, &tmp, nnz, 0, lo_bits, 32, hi_end));
   SBX_TRY(tc_unique(h, n, kout, nnz, flag, uout, out_adj, out_off, m_dev));
-  SBX_TRY(tc_sort(h, n, nnz, &kin, &tmp));
+  SBX_TRY(sbx_sort_keys(h, &kin, &tmp, nnz, 0, lo_bits, 32, hi_end));
   SBX_TRY(tc_unique(h, n, kin, nnz, flag, uin, in_adj, in_off, m_dev + 1));
   return tc_intersect<true>(h, uout, nnz, m_dev, out_off, out_adj, in_off, in_adj, ctr);
 }
