@@ -47,6 +47,7 @@ const sbx_switches &sbx_sw() {
     w.rcm_tie_walk = on_unless_0("SBX_RCM_TIE_WALK");
     w.rcm_tie_spec = on_unless_0("SBX_RCM_TIE_SPEC");
     w.rcm_head_chain = on_unless_0("SBX_RCM_HEAD_CHAIN");
+    w.rcm_bu_blocks = on_unless_0("SBX_RCM_BU_BLOCKS");
     w.bu_ratio = real("SBX_DEBUG_BU_RATIO", 4.0);
     w.gb_backoff = (int)integer("SBX_DEBUG_GB_BACKOFF", 16);
     w.gb_spins = (unsigned)integer("SBX_DEBUG_GB_SPINS", GB_SPINS);

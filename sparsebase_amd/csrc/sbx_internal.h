@@ -208,6 +208,7 @@ struct sbx_switches {
   bool rcm_tie_walk;         // SBX_RCM_TIE_WALK, on; 0: every tie-break through the persistent cone kernels
   bool rcm_tie_spec;         // SBX_RCM_TIE_SPEC, on; 0: the host reads back behind every tie walk before the next sweep
   bool rcm_head_chain;       // SBX_RCM_HEAD_CHAIN, on; 0: a read-back between the first sweep's head run and its chain
+  bool rcm_bu_blocks;        // SBX_RCM_BU_BLOCKS, on; 0: the bottom-up kernels that give a lane to every vertex
   double bu_ratio;           // SBX_DEBUG_BU_RATIO, 4: frontier / unvisited edges above which an ordered level goes bottom-up
   int gb_backoff;            // SBX_DEBUG_GB_BACKOFF, 16: calls kept off the persistent kernels after a barrier gave up
   unsigned gb_spins;         // SBX_DEBUG_GB_SPINS, GB_SPINS: polls a grid barrier waits before it gives up (tests: 0)

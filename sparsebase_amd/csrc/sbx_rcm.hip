@@ -144,14 +144,19 @@ __device__ __forceinline__ int64_t deg_unit_len(int64_t n) { return ((n + DEG_UN
 
 // (The call's three n-sized fills ride along — component sizes 0, distances and parent positions UNSEEN: as
 // hipMemsetAsync calls they cost the host ~25 us of enqueueing at the head of the call, with the GPU idle.)
+// (And the empty-row bitmap of the bottom-up levels, ebits: bit v set when row v is empty.  A unit starts at a multiple of
+// 64 and walks 64 vertices at a time, so a step's ballot is one aligned 64-bit word; lanes past n do not vote and leave
+// zeros, and the bitmaps are sized for the last 64-bit word: sbx_rcm_reorder.)
 __global__ __launch_bounds__(256) void k_deg_count(const X *__restrict__ rp, int64_t n, unsigned *__restrict__ ucnt,
                                                    I *__restrict__ csize, unsigned *__restrict__ dist,
-                                                   unsigned *__restrict__ ppos) {
+                                                   unsigned *__restrict__ ppos, unsigned long long *__restrict__ ebits64) {
   const int unit = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = sbx_lane();
   const int64_t len = deg_unit_len(n), v0 = (int64_t)unit * len;
   unsigned mx = 0, fv = UNSEEN, cnt = 0, top = 0;
   for (int64_t v = v0 + lane; v < v0 + len && v < n; v += 64) {
     const unsigned d = (unsigned)(rp[v + 1] - rp[v]);
+    const uint64_t em = __ballot(d == 0);
+    if (lane == 0) ebits64[v >> 6] = em;
     mx = d > mx ? d : mx;
     top += d >= 255u;
     if (d) {
@@ -967,7 +972,158 @@ __global__ __launch_bounds__(256, RCM_HEAVY_MINW) void k_bfs_expand_heavy(const 
 // current frontier (fbits / lpos) and, if it found one, joins the next level.  No atomics
 // on vertex state, no hot words; chosen by the host when the frontier owns more edges
 // than the unvisited remainder.
-// (eight waves per SIMD: the chunk reservation below, which hardly ever runs, would otherwise cost the scans 30 registers)
+//
+// The candidates of a level are the set bits of ~(vbits | ebits): unvisited vertices with a non-empty row (ebits: the
+// empty-row bitmap k_deg_count leaves).  The kernels with the block front end (k_bfs_bottom_up_blocks,
+// k_ubfs_bottom_up_blocks; SBX_RCM_BU_BLOCKS=0 launches the ones that give a lane to every vertex) read that set off the
+// bitmaps instead of walking all n rows for it: a wave takes RCM_BU_B consecutive bitmap words at a time, one word per
+// lane, compacts the candidate ids of the block into a list in LDS and runs the pull 64 list entries at a time.  A
+// block without candidates costs its two word loads — after a sweep's first bottom-up level that is nearly every block.
+#ifndef SBX_RCM_BU_B
+#define SBX_RCM_BU_B 32  // bitmap words (32 vertices each) per block, a power of two up to 64 (a variant build sets it)
+#endif
+constexpr int RCM_BU_B = SBX_RCM_BU_B;
+constexpr int RCM_BU_LANE_BITS = RCM_BU_B * 32 / 64;  // bits of a block a lane compacts
+static_assert(RCM_BU_B >= 2 && RCM_BU_B <= 64 && 32 % RCM_BU_LANE_BITS == 0, "a lane's bits lie in one word of the block");
+typedef unsigned short BuOff;  // a candidate's offset in its block (< 2048)
+// (LDS of a workgroup of the kernels below: the stage, the lists and the block's words.  Their grids are eight workgroups
+// per CU, resident together — see the launch bounds — so eight of them must fit the 160 KB of a gfx950 CU.  Up to
+// B = 32 they do: 17 KB each.  A B = 64 variant takes 25 KB, six per CU — part of what its first levels measured.)
+static_assert(RCM_BU_B > 32 || 8 * (4 * RCM_STAGE * sizeof(I) + 4 * RCM_BU_B * 32 * sizeof(BuOff) +
+                                    4 * RCM_BU_B * sizeof(unsigned) + 128) <= 160 * 1024,
+              "eight workgroups of the block kernels per CU");
+
+// Front end of a block: loads the block's visited and empty-row words (lane i < RCM_BU_B holds word w0 + i; vw returns the
+// visited word), writes the offsets of the candidates, ascending, to the wave's `list` and returns how many there are
+// (wave-uniform).  nwords = ceil(n / 32); the bits of the last word past n are masked.  All 64 lanes call it.
+__device__ __forceinline__ unsigned bu_block_candidates(const unsigned *vbits, const unsigned *__restrict__ ebits, int64_t w0,
+                                                        int64_t nwords, int64_t n, BuOff *list, unsigned &vw) {
+  const int lane = sbx_lane();
+  unsigned cw = 0;
+  vw = 0;
+  if (lane < RCM_BU_B && w0 + lane < nwords) {
+    vw = vbits[w0 + lane];
+    cw = ~(vw | ebits[w0 + lane]);
+    if (w0 + lane == nwords - 1 && (n & 31)) cw &= (1u << (n & 31)) - 1u;
+  }
+  if (!__any(cw != 0)) return 0u;
+  const unsigned word = (unsigned)__shfl((int)cw, lane * RCM_BU_LANE_BITS / 32, 64);
+  unsigned mine = (word >> ((lane * RCM_BU_LANE_BITS) & 31)) & (unsigned)((1ull << RCM_BU_LANE_BITS) - 1ull);
+  const unsigned incl = sbx_wave_inclusive_sum((unsigned)__popc(mine));
+  unsigned at = incl - (unsigned)__popc(mine);
+  __builtin_amdgcn_wave_barrier();  // (the list's readers of the block before are done: one wave, in order)
+  while (mine) {
+    list[at++] = (BuOff)(lane * RCM_BU_LANE_BITS + __builtin_ctz(mine));
+    mine &= mine - 1;
+  }
+  __builtin_amdgcn_wave_barrier();
+  return (unsigned)__shfl((int)incl, 63, 64);
+}
+
+// The pull of up to 64 candidates, one per lane (has: this lane holds one, vertex v): row pointers, the label test, the
+// chunk reservation for rows above RCM_BU_HEAVY, the one-lane scan up to RCM_BU_INLINE entries and the 16-lane groups.
+// All 64 lanes call it.
+__device__ __forceinline__ void bu_pull64(bool has, int64_t v, const X *__restrict__ rp, const X *__restrict__ col,
+                                          const I *__restrict__ label, I comp_label, const unsigned *__restrict__ fbits,
+                                          const unsigned *__restrict__ lpos, unsigned *__restrict__ ppos,
+                                          I *__restrict__ nf_list, RcmDev *__restrict__ dv, uint64_t *__restrict__ heavy,
+                                          uint64_t heavy_cap, WaveStage &st, unsigned long long &scanned) {
+  const int lane = sbx_lane();
+  const int grp = lane / RCM_GROUP, gl = lane % RCM_GROUP;
+  bool cand = false;
+  I s = 0, e = 0;
+  if (has) {
+    s = rp[v];
+    e = rp[v + 1];
+    cand = (e > s) && (label == nullptr || label[v] == comp_label);
+  }
+  // hubs that are still unvisited (a sweep from the periphery meets the largest ones late) would keep one 16-lane
+  // group busy for milliseconds — 64 entries per step of three dependent loads; forcing the bench matrix's widest level
+  // bottom-up showed it: 6.1 ms for that level, 8000 waves waiting for a handful.  Rows above RCM_BU_HEAVY entries are
+  // queued as chunks of RCM_BU_CHUNK for k_bfs_bottom_up_heavy, a wave each (the queue holds nnz / 256 + nnz / 1024
+  // descriptors and more: enough for every such row of the graph)
+  const bool hv = cand && (e - s) > RCM_BU_HEAVY;
+  if (__any(hv)) {  // one reservation per wave: a lane's slots follow those of the lanes before it
+    const unsigned nch = hv ? (unsigned)((e - s + RCM_BU_CHUNK - 1) / RCM_BU_CHUNK) : 0u;
+    const unsigned incl = sbx_wave_inclusive_sum(nch);
+    unsigned at = 0;
+    if (lane == 63) at = atomicAdd(&dv->n_heavy, incl);
+    at = __shfl(at, 63, 64) + incl - nch;
+    if (hv) {
+      if ((uint64_t)at + nch <= heavy_cap) {
+        for (unsigned c = 0; c < nch; c++) heavy[at + c] = ((uint64_t)(uint32_t)v << 32) | c;
+        cand = false;
+      } else {  // a full queue: the row stays with its 16-lane group below, the slots it got in front of the end are voided
+        for (uint64_t q = at; q < heavy_cap; q++) heavy[q] = ~0ull;
+      }
+    }
+  }
+  // low-degree candidates: one lane each (64 independent load chains per wave; the
+  // rows of consecutive vertices are adjacent in col[], so the lanes share lines)
+  const bool small = cand && (e - s) <= RCM_BU_INLINE;
+  if (__any(small)) {
+    // three unrolled phases keep RCM_BU_INLINE independent loads in flight per lane
+    // instead of a 3-deep dependent chain per neighbour
+    const int dg = small ? (int)(e - s) : 0;
+    I us[RCM_BU_INLINE];
+#pragma unroll
+    for (int k = 0; k < RCM_BU_INLINE; k++) us[k] = k < dg ? col[s + k] : (I)-1;
+    unsigned hit = 0;
+#pragma unroll
+    for (int k = 0; k < RCM_BU_INLINE; k++)
+      if (us[k] >= 0 && ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u)) hit |= 1u << k;
+    unsigned best = UNSEEN;
+#pragma unroll
+    for (int k = 0; k < RCM_BU_INLINE; k++) {
+      const unsigned lp = ((hit >> k) & 1u) ? lpos[us[k]] : UNSEEN;
+      best = lp < best ? lp : best;
+    }
+    if (small) scanned += (unsigned)dg;
+    const bool found = small && best != UNSEEN;
+    if (found) ppos[v] = best;
+    stage_push((I)v, found, rp, st, nf_list, dv);
+  }
+  uint64_t todo = __ballot(cand && !small);
+  while (todo) {
+    // the next RCM_VPW candidates, one per 16-lane group
+    uint64_t t = todo;
+    int pick = -1;
+    for (int g = 0; g < RCM_VPW; g++) {
+      const int c = t ? __builtin_ctzll(t) : -1;
+      if (g == grp) pick = c;
+      if (t) t &= t - 1;
+    }
+    todo = t;
+    const I cs = __shfl(s, pick < 0 ? 0 : pick, 64), ce = __shfl(e, pick < 0 ? 0 : pick, 64);
+    unsigned best = UNSEEN;
+    I j = (pick < 0 ? 0 : cs) + gl;
+    const I jend = pick < 0 ? 0 : ce;
+    while (__any(j < jend)) {
+      I us[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) us[k] = (j + k * RCM_GROUP) < jend ? col[j + k * RCM_GROUP] : (I)-1;
+      unsigned hit = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (us[k] >= 0 && ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u)) hit |= 1u << k;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const unsigned lp = ((hit >> k) & 1u) ? lpos[us[k]] : UNSEEN;
+        best = lp < best ? lp : best;
+      }
+      j += 4 * RCM_GROUP;
+    }
+    if (gl == 0 && pick >= 0) scanned += (unsigned)(ce - cs);
+    static_assert(RCM_GROUP == 16, "a group is one DPP row");
+    best = sbx_row16_reduce(best, SbxOpMin());
+    const bool found = (gl == 0) && pick >= 0 && best != UNSEEN;
+    const I nv = __shfl((I)v, pick < 0 ? 0 : pick, 64);  // (the group's vertex is lane `pick`'s)
+    if (found) ppos[nv] = best;
+    stage_push(nv, found, rp, st, nf_list, dv);
+  }
+}
+
+// (eight waves per SIMD: the chunk reservation, which hardly ever runs, would otherwise cost the scans 30 registers)
 __global__ __launch_bounds__(256, 8) void k_bfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
                                                        const I *__restrict__ label, I comp_label,
                                                        const unsigned *__restrict__ vbits,
@@ -979,101 +1135,42 @@ __global__ __launch_bounds__(256, 8) void k_bfs_bottom_up(const X *__restrict__ 
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int lane = sbx_lane();
-  const int grp = lane / RCM_GROUP, gl = lane % RCM_GROUP;
   WaveStage st{s_stage[sbx_wave_in_block()], 0u, 0ull, &dv->nf, &dv->fedges};
   unsigned long long scanned = 0;
   for (int64_t base = wave * 64; base < n; base += nwaves * 64) {
     const int64_t v = base + lane;
-    bool cand = false;
-    I s = 0, e = 0;
-    if (v < n && !((vbits[v >> 5] >> (v & 31)) & 1u)) {
-      s = rp[v];
-      e = rp[v + 1];
-      cand = (e > s) && (label == nullptr || label[v] == comp_label);
-    }
-    // hubs that are still unvisited (a sweep from the periphery meets the largest ones late) would keep one 16-lane
-    // group busy for milliseconds — 64 entries per step of three dependent loads; forcing the bench matrix's widest level
-    // bottom-up showed it: 6.1 ms for that level, 8000 waves waiting for a handful.  Rows above RCM_BU_HEAVY entries are
-    // queued as chunks of RCM_BU_CHUNK for k_bfs_bottom_up_heavy, a wave each (the queue holds nnz / 256 + nnz / 1024
-    // descriptors and more: enough for every such row of the graph)
-    const bool hv = cand && (e - s) > RCM_BU_HEAVY;
-    if (__any(hv)) {  // one reservation per wave: a lane's slots follow those of the lanes before it
-      const unsigned nch = hv ? (unsigned)((e - s + RCM_BU_CHUNK - 1) / RCM_BU_CHUNK) : 0u;
-      const unsigned incl = sbx_wave_inclusive_sum(nch);
-      unsigned at = 0;
-      if (lane == 63) at = atomicAdd(&dv->n_heavy, incl);
-      at = __shfl(at, 63, 64) + incl - nch;
-      if (hv) {
-        if ((uint64_t)at + nch <= heavy_cap) {
-          for (unsigned c = 0; c < nch; c++) heavy[at + c] = ((uint64_t)(uint32_t)v << 32) | c;
-          cand = false;
-        } else {  // a full queue: the row stays with its 16-lane group below, the slots it got in front of the end are voided
-          for (uint64_t q = at; q < heavy_cap; q++) heavy[q] = ~0ull;
-        }
-      }
-    }
-    // low-degree candidates: one lane each (64 independent load chains per wave; the
-    // rows of consecutive vertices are adjacent in col[], so the lanes share lines)
-    const bool small = cand && (e - s) <= RCM_BU_INLINE;
-    if (__any(small)) {
-      // three unrolled phases keep RCM_BU_INLINE independent loads in flight per lane
-      // instead of a 3-deep dependent chain per neighbour
-      const int dg = small ? (int)(e - s) : 0;
-      I us[RCM_BU_INLINE];
-#pragma unroll
-      for (int k = 0; k < RCM_BU_INLINE; k++) us[k] = k < dg ? col[s + k] : (I)-1;
-      unsigned hit = 0;
-#pragma unroll
-      for (int k = 0; k < RCM_BU_INLINE; k++)
-        if (us[k] >= 0 && ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u)) hit |= 1u << k;
-      unsigned best = UNSEEN;
-#pragma unroll
-      for (int k = 0; k < RCM_BU_INLINE; k++) {
-        const unsigned lp = ((hit >> k) & 1u) ? lpos[us[k]] : UNSEEN;
-        best = lp < best ? lp : best;
-      }
-      if (small) scanned += (unsigned)dg;
-      const bool found = small && best != UNSEEN;
-      if (found) ppos[v] = best;
-      stage_push((I)v, found, rp, st, nf_list, dv);
-    }
-    uint64_t todo = __ballot(cand && !small);
-    while (todo) {
-      // the next RCM_VPW candidates, one per 16-lane group
-      uint64_t t = todo;
-      int pick = -1;
-      for (int g = 0; g < RCM_VPW; g++) {
-        const int c = t ? __builtin_ctzll(t) : -1;
-        if (g == grp) pick = c;
-        if (t) t &= t - 1;
-      }
-      todo = t;
-      const I cs = __shfl(s, pick < 0 ? 0 : pick, 64), ce = __shfl(e, pick < 0 ? 0 : pick, 64);
-      unsigned best = UNSEEN;
-      I j = (pick < 0 ? 0 : cs) + gl;
-      const I jend = pick < 0 ? 0 : ce;
-      while (__any(j < jend)) {
-        I us[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) us[k] = (j + k * RCM_GROUP) < jend ? col[j + k * RCM_GROUP] : (I)-1;
-        unsigned hit = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (us[k] >= 0 && ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u)) hit |= 1u << k;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const unsigned lp = ((hit >> k) & 1u) ? lpos[us[k]] : UNSEEN;
-          best = lp < best ? lp : best;
-        }
-        j += 4 * RCM_GROUP;
-      }
-      if (gl == 0 && pick >= 0) scanned += (unsigned)(ce - cs);
-      static_assert(RCM_GROUP == 16, "a group is one DPP row");
-      best = sbx_row16_reduce(best, SbxOpMin());
-      const bool found = (gl == 0) && pick >= 0 && best != UNSEEN;
-      const I nv = (I)(base + (pick < 0 ? 0 : pick));
-      if (found) ppos[nv] = best;
-      stage_push(nv, found, rp, st, nf_list, dv);
+    const bool has = v < n && !((vbits[v >> 5] >> (v & 31)) & 1u);
+    bu_pull64(has, v, rp, col, label, comp_label, fbits, lpos, ppos, nf_list, dv, heavy, heavy_cap, st, scanned);
+  }
+  stage_end_block(st, nf_list, dv, scanned, true);
+}
+
+// the same level with the block front end (see above): the candidates come off the bitmaps
+__global__ __launch_bounds__(256, 8) void k_bfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
+                                                              const I *__restrict__ label, I comp_label,
+                                                              const unsigned *__restrict__ vbits,
+                                                              const unsigned *__restrict__ ebits,
+                                                              const unsigned *__restrict__ fbits,
+                                                              const unsigned *__restrict__ lpos, unsigned *__restrict__ ppos,
+                                                              I *__restrict__ nf_list, int64_t n, RcmDev *__restrict__ dv,
+                                                              uint64_t *__restrict__ heavy, uint64_t heavy_cap) {
+  __shared__ I s_stage[4][RCM_STAGE];
+  __shared__ BuOff s_list[4][RCM_BU_B * 32];
+  // (the wave's number in a scalar register: the block loop and the LDS slices then cost no vector registers)
+  const int wv = __builtin_amdgcn_readfirstlane(sbx_wave_in_block());
+  const int64_t wave = (int64_t)blockIdx.x * 4 + wv, nwaves = (int64_t)gridDim.x * 4;
+  const int lane = sbx_lane();
+  BuOff *list = s_list[wv];
+  WaveStage st{s_stage[wv], 0u, 0ull, &dv->nf, &dv->fedges};
+  unsigned long long scanned = 0;
+  const int64_t nwords = (n + 31) / 32;
+  for (int64_t w0 = wave * RCM_BU_B; w0 < nwords; w0 += nwaves * RCM_BU_B) {
+    unsigned vw;
+    const unsigned total = bu_block_candidates(vbits, ebits, w0, nwords, n, list, vw);
+    for (unsigned i = 0; i < total; i += 64) {
+      const bool has = i + lane < total;
+      const int64_t v = w0 * 32 + (has ? (int64_t)list[i + lane] : 0);
+      bu_pull64(has, v, rp, col, label, comp_label, fbits, lpos, ppos, nf_list, dv, heavy, heavy_cap, st, scanned);
     }
   }
   stage_end_block(st, nf_list, dv, scanned, true);
@@ -1952,6 +2049,7 @@ struct BfsBuffers {
   bool *claim_clean;  // the claim bytes of the unordered sweeps are all zero (a finished sweep leaves them that way)
   const X *rp, *col;
   unsigned *vbits, *fbits, *lpos, *ppos;
+  const unsigned *ebits;  // bit v: row v is empty (k_deg_count, at the head of the call on the caller's stream)
   const I *label;
   int64_t nnz;
   I *q;         // visiting order of the current BFS (levels concatenated)
@@ -2089,9 +2187,14 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_mark_frontier, dim3(sbx_grid_for(fsize, 256, 1024)), dim3(256),
                     (const I *)(b.q + off), fsize, b.fbits, b.lpos);
       }
-      SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                  (const unsigned *)b.vbits, (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list,
-                  b.n, b.dv, b.heavy, b.heavy_cap);
+      if (sbx_sw().rcm_bu_blocks)
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_blocks, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
+                    (const unsigned *)b.vbits, (const unsigned *)b.ebits, (const unsigned *)b.fbits, (const unsigned *)b.lpos,
+                    b.ppos, b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
+      else
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
+                    (const unsigned *)b.vbits, (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list,
+                    b.n, b.dv, b.heavy, b.heavy_cap);
       if (b.max_deg > (unsigned)RCM_BU_HEAVY)
         SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_heavy, dim3(8 * (unsigned)h->num_cus), dim3(256), b.rp, b.col,
                     (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list, b.dv,
@@ -2441,6 +2544,111 @@ __global__ __launch_bounds__(256) void k_ubfs_collect(unsigned char *__restrict_
 // four entries, where a 16-lane group fetches 64 at a time (16 -> 1024: 33 M -> 12 M entries scanned bottom-up on the
 // bench matrix, the kernel 0.64 -> 0.36 ms per RCM; beyond 1024 nothing changes)
 constexpr int UB_INLINE = 1024;
+
+// The pull of up to 64 candidates, one per lane (has: this lane holds one, vertex v): row pointers, the label test, the
+// one-lane scan with its early exit and the 16-lane groups.  Returns whether the lane's vertex found a neighbour in the
+// frontier; distance and queue are written here, the bitmaps by the caller.  All 64 lanes call it.
+__device__ __forceinline__ bool ubu_pull64(bool has, int64_t v, const X *__restrict__ rp, const X *__restrict__ col,
+                                           const I *__restrict__ label, I comp_label, const unsigned *__restrict__ fbits,
+                                           unsigned *__restrict__ dist, unsigned level, I *__restrict__ nf_list,
+                                           RcmDev *dv, WaveStage &st, unsigned long long &scanned) {
+  const int lane = sbx_lane();
+  const int grp = lane / RCM_GROUP, gl = lane % RCM_GROUP;
+  bool cand = false;
+  I s = 0, e = 0;
+  if (has) {
+    s = rp[v];
+    e = rp[v + 1];
+    cand = (e > s) && (label == nullptr || label[v] == comp_label);
+  }
+  const bool small = cand && (e - s) <= UB_INLINE;
+  bool found = false;
+  if (__any(small)) {
+    // four entries at a time, every load of a batch in flight together; a wave stops as soon as every one of its small
+    // candidates has either found a frontier neighbour or run out of entries (most have one to four of them)
+    const int dg = small ? (int)(e - s) : 0;
+    int done = 0;
+    for (int k0 = 0; k0 < UB_INLINE; k0 += 4) {
+      if (!__any(small && !found && dg > k0)) break;
+      I us[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) us[k] = (small && !found && k0 + k < dg) ? col[s + k0 + k] : (I)-1;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (us[k] >= 0) {
+          done++;
+          if ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u) found = true;
+        }
+    }
+    scanned += (unsigned)done;
+  }
+  uint64_t todo = __ballot(cand && !small);
+  uint64_t big_found = 0;  // lanes (vertices) of this wave's 64 that a group found a frontier neighbour for
+  while (todo) {
+    uint64_t t = todo;
+    int pick = -1;
+    for (int g = 0; g < RCM_VPW; g++) {
+      const int c = t ? __builtin_ctzll(t) : -1;
+      if (g == grp) pick = c;
+      if (t) t &= t - 1;
+    }
+    todo = t;
+    const I cs = __shfl(s, pick < 0 ? 0 : pick, 64), ce = __shfl(e, pick < 0 ? 0 : pick, 64);
+    bool hit = false;
+    I j = (pick < 0 ? 0 : cs) + gl;
+    const I jend = pick < 0 ? 0 : ce;
+    unsigned seen = 0;
+    while (__any(j < jend)) {
+      I us[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) us[k] = (j + k * RCM_GROUP) < jend ? col[j + k * RCM_GROUP] : (I)-1;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (us[k] >= 0) {
+          seen++;
+          if ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u) hit = true;
+        }
+      // a group whose vertex has been found stops (its 16 lanes agree through the row-wide OR)
+      const unsigned any_hit = sbx_row16_reduce(hit ? 1u : 0u, SbxOpMax());
+      j = any_hit ? jend : j + 4 * RCM_GROUP;
+    }
+    scanned += seen;
+    const unsigned ghit = sbx_row16_reduce(hit ? 1u : 0u, SbxOpMax());
+    // the lane that holds a group's vertex is lane `pick` of the wave: collect the groups' results for their owners
+#pragma unroll
+    for (int g = 0; g < RCM_VPW; g++) {
+      const int pk = __shfl(pick, g * RCM_GROUP, 64);
+      const unsigned gh = __shfl(ghit, g * RCM_GROUP, 64);
+      if (gh && pk >= 0) big_found |= (uint64_t)1 << pk;
+    }
+  }
+  found = found || ((big_found >> lane) & 1ull);
+  if (found) dist[v] = level;
+  stage_push((I)v, found, rp, st, nf_list, dv);
+  return found;
+}
+
+// the chain election at the end of both unordered bottom-up kernels: the last workgroup out moves the chain on
+__device__ __forceinline__ void ubu_chain_end(RcmDev *dv, int chain, const ChainInit &ci) {
+  if (chain && threadIdx.x == 0) {
+    // This workgroup's additions to the level's counters were returning atomics or thread 0's own: waiting for the
+    // latter is all the ordering the election needs (the counters live in L2 and are read there).  A release fence
+    // here — a write-back of the L2 per workgroup, 2048 of them — doubled the kernel's time.
+    // Words under the invariant (see gb_wait): the level's counters unf[] / ufedges[] / n_heavy (returning atomics of the
+    // waves, or thread 0's own adds), uc_done (the election), and what uc_advance / uc_begin write for the next link
+    // of the chain (uc_mode, uc_level, uc_off, ...: read by kernels launched behind this one, i.e. behind a kernel boundary).
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    SBX_GB_RELEASE();
+    if (atomicAdd(&dv->uc_done, 1u) == gridDim.x - 1) {
+      SBX_GB_ACQUIRE();
+      dv->uc_done = 0;
+      if (chain == 2) uc_begin(dv, ci);
+      else dv->uc_flips++;
+      uc_advance(dv, ci.bu_ratio);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
                                                         const I *__restrict__ label, I comp_label,
                                                         unsigned *vbits, const unsigned *__restrict__ fbits,
@@ -2459,7 +2667,6 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int lane = sbx_lane();
-  const int grp = lane / RCM_GROUP, gl = lane % RCM_GROUP;
   const int slot = (int)(level & 1u);
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // (as k_ubfs_collect: the other level slot is cleared for the next level)
     dv->unf[slot ^ 1] = 0;
@@ -2471,75 +2678,8 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
   unsigned long long scanned = 0;
   for (int64_t base = wave * 64; base < n; base += nwaves * 64) {
     const int64_t v = base + lane;
-    bool cand = false;
-    I s = 0, e = 0;
-    if (v < n && !((vbits[v >> 5] >> (v & 31)) & 1u)) {
-      s = rp[v];
-      e = rp[v + 1];
-      cand = (e > s) && (label == nullptr || label[v] == comp_label);
-    }
-    const bool small = cand && (e - s) <= UB_INLINE;
-    bool found = false;
-    if (__any(small)) {
-      // four entries at a time, every load of a batch in flight together; a wave stops as soon as every one of its small
-      // candidates has either found a frontier neighbour or run out of entries (most have one to four of them)
-      const int dg = small ? (int)(e - s) : 0;
-      int done = 0;
-      for (int k0 = 0; k0 < UB_INLINE; k0 += 4) {
-        if (!__any(small && !found && dg > k0)) break;
-        I us[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) us[k] = (small && !found && k0 + k < dg) ? col[s + k0 + k] : (I)-1;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (us[k] >= 0) {
-            done++;
-            if ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u) found = true;
-          }
-      }
-      scanned += (unsigned)done;
-    }
-    uint64_t todo = __ballot(cand && !small);
-    uint64_t big_found = 0;  // lanes (vertices) of this wave's 64 that a group found a frontier neighbour for
-    while (todo) {
-      uint64_t t = todo;
-      int pick = -1;
-      for (int g = 0; g < RCM_VPW; g++) {
-        const int c = t ? __builtin_ctzll(t) : -1;
-        if (g == grp) pick = c;
-        if (t) t &= t - 1;
-      }
-      todo = t;
-      const I cs = __shfl(s, pick < 0 ? 0 : pick, 64), ce = __shfl(e, pick < 0 ? 0 : pick, 64);
-      bool hit = false;
-      I j = (pick < 0 ? 0 : cs) + gl;
-      const I jend = pick < 0 ? 0 : ce;
-      unsigned seen = 0;
-      while (__any(j < jend)) {
-        I us[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) us[k] = (j + k * RCM_GROUP) < jend ? col[j + k * RCM_GROUP] : (I)-1;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (us[k] >= 0) {
-            seen++;
-            if ((fbits[us[k] >> 5] >> (us[k] & 31)) & 1u) hit = true;
-          }
-        // a group whose vertex has been found stops (its 16 lanes agree through the row-wide OR)
-        const unsigned any_hit = sbx_row16_reduce(hit ? 1u : 0u, SbxOpMax());
-        j = any_hit ? jend : j + 4 * RCM_GROUP;
-      }
-      scanned += seen;
-      const unsigned ghit = sbx_row16_reduce(hit ? 1u : 0u, SbxOpMax());
-      // the lane that holds a group's vertex is lane `pick` of the wave: collect the groups' results for their owners
-#pragma unroll
-      for (int g = 0; g < RCM_VPW; g++) {
-        const int pk = __shfl(pick, g * RCM_GROUP, 64);
-        const unsigned gh = __shfl(ghit, g * RCM_GROUP, 64);
-        if (gh && pk >= 0) big_found |= (uint64_t)1 << pk;
-      }
-    }
-    found = found || ((big_found >> lane) & 1ull);
+    const bool has = v < n && !((vbits[v >> 5] >> (v & 31)) & 1u);
+    const bool found = ubu_pull64(has, v, rp, col, label, comp_label, fbits, dist, level, nf_list, dv, st, scanned);
     // lane = vertex and the wave owns the two bitmap words of its 64 vertices: the level is published right here —
     // visited bit (only this wave ever tests it), next frontier word (every word is written, so the array needs no
     // clearing), distance, queue — and needs no collection pass
@@ -2549,27 +2689,73 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
       nbits[(base >> 5) + (lane >> 5)] = wbits;
       if (wbits) vbits[(base >> 5) + (lane >> 5)] |= wbits;
     }
-    if (found) dist[v] = level;
-    stage_push((I)v, found, rp, st, nf_list, dv);
   }
   stage_end_block(st, nf_list, dv, scanned, true);
-  if (chain && threadIdx.x == 0) {
-    // This workgroup's additions to the level's counters were returning atomics or thread 0's own: waiting for the
-    // latter is all the ordering the election needs (the counters live in L2 and are read there).  A release fence
-    // here — a write-back of the L2 per workgroup, 2048 of them — doubled the kernel's time.
-    // Words under the invariant (see gb_wait): the level's counters unf[] / ufedges[] / n_heavy (returning atomics of the
-    // waves, or thread 0's own adds), uc_done (the election), and what uc_advance / uc_begin write for the next link
-    // of the chain (uc_mode, uc_level, uc_off, ...: read by kernels launched behind this one, i.e. behind a kernel boundary).
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    SBX_GB_RELEASE();
-    if (atomicAdd(&dv->uc_done, 1u) == gridDim.x - 1) {
-      SBX_GB_ACQUIRE();
-      dv->uc_done = 0;
-      if (chain == 2) uc_begin(dv, ci);
-      else dv->uc_flips++;
-      uc_advance(dv, ci.bu_ratio);
+  ubu_chain_end(dv, chain, ci);
+}
+
+// the same level with the block front end (see k_bfs_bottom_up_blocks): a wave owns the words of its block, so it
+// publishes them as the kernel above does — the found candidates OR their bit into a copy of the block's next-frontier
+// words in LDS, and when the block is done lane i writes word i: nbits always (every word below ceil(n / 32) is written,
+// also those of a block without candidates; no reader looks past vertex n - 1), vbits where something was found
+// (eight waves per SIMD, as k_bfs_bottom_up: the grid is eight workgroups per CU and a wave has one block or two — a
+// workgroup that had to wait for a place would double the level's time)
+__global__ __launch_bounds__(256, 8) void k_ubfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
+                                                               const I *__restrict__ label, I comp_label,
+                                                               unsigned *vbits, const unsigned *__restrict__ ebits,
+                                                               const unsigned *__restrict__ fbits,
+                                                               unsigned *__restrict__ nbits, unsigned *__restrict__ dist,
+                                                               unsigned level, I *__restrict__ nf_list, int64_t n,
+                                                               RcmDev *dv, int chain, ChainInit ci) {
+  if (chain == 1) {  // (as in k_ubfs_bottom_up)
+    if (dv->uc_mode != UC_BU) return;
+    level = dv->uc_level + 1;
+    nf_list += dv->uc_off + dv->uc_size;
+  }
+  __shared__ I s_stage[4][RCM_STAGE];
+  __shared__ BuOff s_list[4][RCM_BU_B * 32];
+  __shared__ unsigned s_next[4][RCM_BU_B];
+  const int wv = __builtin_amdgcn_readfirstlane(sbx_wave_in_block());
+  const int64_t wave = (int64_t)blockIdx.x * 4 + wv, nwaves = (int64_t)gridDim.x * 4;
+  const int lane = sbx_lane();
+  BuOff *list = s_list[wv];
+  unsigned *next = s_next[wv];
+  const int slot = (int)(level & 1u);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    dv->unf[slot ^ 1] = 0;
+    dv->ufedges[slot ^ 1] = 0;
+    dv->n_heavy = 0;
+    dv->hub_overflow = 0;
+  }
+  WaveStage st{s_stage[wv], 0u, 0ull, &dv->unf[slot], &dv->ufedges[slot]};
+  unsigned long long scanned = 0;
+  const int64_t nwords = (n + 31) / 32;
+  for (int64_t w0 = wave * RCM_BU_B; w0 < nwords; w0 += nwaves * RCM_BU_B) {
+    unsigned vw;
+    const unsigned total = bu_block_candidates(vbits, ebits, w0, nwords, n, list, vw);
+    const bool mine = lane < RCM_BU_B && w0 + lane < nwords;  // this lane holds (and writes) word w0 + lane
+    if (total == 0) {
+      if (mine) nbits[w0 + lane] = 0u;
+      continue;
+    }
+    if (lane < RCM_BU_B) next[lane] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    for (unsigned i = 0; i < total; i += 64) {
+      const bool has = i + lane < total;
+      const unsigned o = has ? (unsigned)list[i + lane] : 0u;
+      const int64_t v = w0 * 32 + o;
+      const bool found = ubu_pull64(has, v, rp, col, label, comp_label, fbits, dist, level, nf_list, dv, st, scanned);
+      if (found) atomicOr(&next[o >> 5], 1u << (o & 31));
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (mine) {
+      const unsigned wbits = next[lane];
+      nbits[w0 + lane] = wbits;
+      if (wbits) vbits[w0 + lane] = vw | wbits;
     }
   }
+  stage_end_block(st, nf_list, dv, scanned, true);
+  ubu_chain_end(dv, chain, ci);
 }
 
 // deepest level: smallest degree, then the vertices that have it — marked in the cone bitmap, listed (the list counter
@@ -3673,6 +3859,17 @@ __global__ __launch_bounds__(256) void k_check_closed(const X *__restrict__ rp, 
   }
 }
 
+// one unordered bottom-up level: the kernel with the block front end, or (SBX_RCM_BU_BLOCKS=0) the one with a lane per vertex
+static void launch_ubfs_bottom_up(sbx_handle_t h, const BfsBuffers &b, unsigned grid, I comp_label, const unsigned *cur_f,
+                                  unsigned *cur_n, unsigned *dist, unsigned level, I *nf_list, int chain, const ChainInit &ci) {
+  if (sbx_sw().rcm_bu_blocks)
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up_blocks, dim3(grid), dim3(256), b.rp, b.col, b.label, comp_label, b.vbits,
+                b.ebits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+  else
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(grid), dim3(256), b.rp, b.col, b.label, comp_label, b.vbits,
+                cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+}
+
 // One unordered sweep from fixed_root (>= 0) or dv->root: level sets only.  *too_deep is set when the sweep passed the
 // depth limit (ub_max_levels) and was abandoned: the caller runs the ordered sweep instead.
 static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, unsigned *nbits_buf, unsigned *cone,
@@ -3737,8 +3934,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
                     (const unsigned *)b.vbits, (const unsigned *)dist, 0u, b.n, cur_f, (const RcmDev *)b.dv);
         unsigned *cf = cur_f, *cn = cur_n;
         for (int i = 0; i <= spec_len; i++) {
-          SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                      b.vbits, (const unsigned *)cf, cn, dist, 0u, b.q, b.n, b.dv, 1, ci0);
+          launch_ubfs_bottom_up(h, b, max_grid, comp_label, cf, cn, dist, 0u, b.q, 1, ci0);
           std::swap(cf, cn);
         }
         SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
@@ -3819,8 +4015,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
                     (const unsigned *)b.vbits, (const unsigned *)dist, level, b.n, cur_f, (const RcmDev *)nullptr);
       // publishes the level itself (bitmaps, distances, queue): no collection pass
-      SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                  b.vbits, (const unsigned *)cur_f, cur_n, dist, level + 1, q_next, b.n, b.dv, chain_len > 0 ? 2 : 0, ci);
+      launch_ubfs_bottom_up(h, b, max_grid, comp_label, cur_f, cur_n, dist, level + 1, q_next, chain_len > 0 ? 2 : 0, ci);
       std::swap(cur_f, cur_n);
     } else {
       const unsigned waves_needed = (fsize + RCM_VPW - 1) / RCM_VPW;
@@ -3847,8 +4042,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
       // A sweep of the bench matrix: a small run, three bottom-up levels, a small run — five round trips, now two.
       unsigned *cf = cur_f, *cn = cur_n;
       for (int i = 0; i < chain_len; i++) {
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                    b.vbits, (const unsigned *)cf, cn, dist, 0u, b.q, b.n, b.dv, 1, ci);
+        launch_ubfs_bottom_up(h, b, max_grid, comp_label, cf, cn, dist, 0u, b.q, 1, ci);
         std::swap(cf, cn);
       }
       SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
@@ -4117,6 +4311,8 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   SBX_TRY(sbx_salloc(h, 3 * bm_words, &vbits));
   fbits = vbits + bm_words;
   cbits = fbits + bm_words;
+  unsigned *ebits;  // the empty rows (k_deg_count below): with vbits, the candidates of every bottom-up level
+  SBX_TRY(sbx_salloc(h, bm_words, &ebits));
   SBX_TRY(sbx_salloc(h, (size_t)n, &q_small));
   SBX_TRY(sbx_salloc(h, (size_t)n, &lpos));
   const size_t heavy_cap = (size_t)(nnz / RCM_LIGHT + nnz / RCM_CHUNK + 1024);
@@ -4130,7 +4326,8 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   // (1) global (degree,id) rank used by the Cuthill-McKee keys; first non-isolated vertex
   unsigned *ucnt = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)DEG_UNITS * 4, &ucnt));  // per unit: non-empty rows, largest degree, first non-empty vertex, rows of 255+ entries
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_count, dim3(DEG_UNITS / 4), dim3(256), rp, n, ucnt, csize, dist, ppos);
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_count, dim3(DEG_UNITS / 4), dim3(256), rp, n, ucnt, csize, dist, ppos,
+              (unsigned long long *)ebits);
   SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_reduce, dim3(1), dim3(1024), (const unsigned *)ucnt, dv);
   SBX_LAUNCH_CHECK(h);
   // after a grid barrier gave up (a GPU shared with another process, see gb_wait) the next few calls on this handle do
@@ -4211,6 +4408,9 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   b.tie_unverified = &tie_unverified;
   b.side_stage = nullptr, b.side_event = nullptr, b.side_joined = nullptr, b.last_read = nullptr, b.last_read_joined = nullptr;
   b.rp = rp; b.col = col; b.vbits = vbits; b.fbits = fbits; b.lpos = lpos; b.ppos = ppos; b.label = nullptr;
+  // (every sweep of the call, on this stream or on one forked from it later, runs behind k_deg_count above — the lazy
+  // read-back of its counts changes what the HOST knows, not the stream order — so no level meets an unbuilt bitmap)
+  b.ebits = ebits;
   b.nnz = nnz; b.q = q; b.nf_list = nf_list; b.heavy = heavy; b.heavy_cap = heavy_cap;
   SBX_TRY(sbx_salloc(h, (size_t)std::max<int64_t>((int64_t)h->num_cus * 8, RCM_DIR_MAX), &b.hub_dir));
   b.ka = ka; b.kb = kb; b.drank = drank; b.dorder = dorder; b.n_ranked = n_ranked; b.dv = dv; b.n = n;
