@@ -30,6 +30,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbx.h"))
     hs.append(os.path.join(ROOT, "include", "sbx_text.h"))
     hs.append(os.path.join(ROOT, "include", "sbx_stats.h"))
+    hs.append(os.path.join(ROOT, "include", "sbio.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h and include/sbx_stats.h
+"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h and include/sbio.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -143,6 +143,14 @@ STATS_PROTOTYPES = {
     "sbxstat_csr_off_diag_block_nnz": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _i64, _i64, C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbio.h declares (tests/test_io_abi.py checks header <-> library <-> this table): the dense side of
+# the Matrix Market path, prefix `sbio_`
+IO_PROTOTYPES = {
+    "sbio_mtx_parse_values": ([_H, _int, _vp, _i64, _i64, _vp], _int),
+    "sbio_dense_to_coo": ([_H, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, C.POINTER(_i64)], _int),
+    "sbio_coo_to_dense_vector": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+}
+
 _lib = None
 
 
@@ -155,7 +163,7 @@ def load():
                               "(there is no CPU fallback for the HIP hot path)")
         lib = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
-                                           list(STATS_PROTOTYPES.items())):
+                                           list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -344,13 +344,14 @@ SBX_HD int sbx_parse_integer(const char *s, int64_t len, long long *out) {
   if (i < len && (s[i] == '+' || s[i] == '-')) { neg = s[i] == '-'; i++; }
   if (i >= len) return 1;
   unsigned long long v = 0;
+  const unsigned long long limit = 9223372036854775807ull + (unsigned)neg;  // (-2^63 is a value, +2^63 is not)
   for (; i < len; i++) {
     if (s[i] < '0' || s[i] > '9') return 1;
     if (v > 922337203685477580ull) return 1;
     v = v * 10u + (unsigned)(s[i] - '0');
-    if (v > 9223372036854775807ull) return 1;
+    if (v > limit) return 1;
   }
-  *out = neg ? -(long long)v : (long long)v;
+  *out = (long long)(neg ? 0ull - v : v);  // (in unsigned arithmetic: -2^63 has no positive counterpart)
   return 0;
 }
 

@@ -16,79 +16,11 @@
 #include "sbx_dec2bin.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
+#include "sbx_mtx_tokens.h"
 
 namespace {
 
-constexpr int MX_THREADS = 256;
-constexpr int MX_BPT = 16;                       // text bytes per thread
-constexpr int MX_TILE = MX_THREADS * MX_BPT;     // text bytes per workgroup
-
 enum : unsigned { MX_BAD_INDEX = 1u, MX_BAD_VALUE = 2u, MX_TOO_MANY_DIGITS = 4u, MX_INDEX_RANGE = 8u };
-
-__device__ __forceinline__ bool mx_space(char c) {
-  return c == ' ' || c == '\n' || c == '\t' || c == '\r' || c == '\v' || c == '\f';
-}
-
-// token starts of this thread's MX_BPT bytes as a bit mask
-__device__ __forceinline__ unsigned mx_starts(const char *__restrict__ text, int64_t bytes, int64_t p0) {
-  static_assert(MX_BPT == 16, "one 16-byte load per thread");
-  unsigned mask = 0;
-  const char before = p0 == 0 ? ' ' : text[p0 - 1];
-  if (p0 + MX_BPT <= bytes && (((uintptr_t)text + (uintptr_t)p0) & 15) == 0) {
-    // the thread's 16 bytes in one load (byte by byte, under the end-of-text test, the compiler made them 17 loads
-    // that wait for one another: tools/isa_waits.py)
-    const uint4 v = *(const uint4 *)(text + p0);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    bool prev_space = mx_space(before);
-#pragma unroll
-    for (int k = 0; k < MX_BPT; k++) {
-      const bool sp = mx_space((char)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu));
-      if (!sp && prev_space) mask |= 1u << k;
-      prev_space = sp;
-    }
-    return mask;
-  }
-  bool prev_space = mx_space(before);
-#pragma unroll
-  for (int k = 0; k < MX_BPT; k++) {
-    if (p0 + k >= bytes) break;
-    const bool sp = mx_space(text[p0 + k]);
-    if (!sp && prev_space) mask |= 1u << k;
-    prev_space = sp;
-  }
-  return mask;
-}
-
-__global__ __launch_bounds__(MX_THREADS) void k_mtx_count(const char *__restrict__ text, int64_t bytes,
-                                                          unsigned *__restrict__ tile_tokens) {
-  __shared__ unsigned s_red[MX_THREADS / 64 + 1];
-  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
-  const unsigned c = p0 < bytes ? (unsigned)__popc(mx_starts(text, bytes, p0)) : 0u;
-  const unsigned tot = sbx_block_sum<unsigned, MX_THREADS>(c, s_red);
-  if (threadIdx.x == 0) tile_tokens[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(MX_THREADS) void k_mtx_offsets(const char *__restrict__ text, int64_t bytes,
-                                                            const unsigned *__restrict__ tile_base,
-                                                            int64_t max_tokens, unsigned *__restrict__ tok_off) {
-  __shared__ unsigned s_scan[MX_THREADS / 64 + 1];
-  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
-  unsigned mask = p0 < bytes ? mx_starts(text, bytes, p0) : 0u;
-  unsigned all;
-  unsigned t = tile_base[blockIdx.x] + sbx_block_exclusive_sum<unsigned, MX_THREADS>((unsigned)__popc(mask), s_scan, &all);
-  while (mask) {
-    const int k = __ffs(mask) - 1;
-    mask &= mask - 1;
-    if ((int64_t)t < max_tokens) tok_off[t] = (unsigned)(p0 + k);
-    t++;
-  }
-}
-
-__device__ __forceinline__ int64_t mx_token_len(const char *__restrict__ text, int64_t bytes, int64_t start) {
-  int64_t e = start;
-  while (e < bytes && !mx_space(text[e])) e++;
-  return e - start;
-}
 
 // one thread per entry: indices, value, mirror flag
 template <int VKIND /*0 none, 1 integer, 2 float, 3 double*/, int VB>
@@ -264,12 +196,6 @@ __global__ __launch_bounds__(MX_THREADS) void k_edge_compact(const int32_t *__re
   if (VB == 4) ((uint32_t *)val_out)[o] = ((const uint32_t *)val)[i];
   if (VB == 8) ((uint64_t *)val_out)[o] = ((const uint64_t *)val)[i];
 }
-
-struct NestGuard {
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
-  ~NestGuard() { h->nest--; }
-};
 
 }  // namespace
 

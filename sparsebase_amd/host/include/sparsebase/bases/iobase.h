@@ -1,6 +1,9 @@
-// sparsebase/bases/iobase.h — the reading facade the examples use (reference:
-// bases/iobase.h:46-90 ReadMTXToCSR / ReadMTXToCOO, :161-195 ReadEdgeListToCSR / ReadEdgeListToCOO);
-// the text files are parsed on the GPU.  Binary (SbFF) facade: :195-295.
+// sparsebase/bases/iobase.h — the reading and writing facade the examples use (reference:
+// bases/iobase.h:46-98 ReadMTXToCSR / ReadMTXToCOO / ReadMTXToArray, :161-195 ReadEdgeListToCSR / ReadEdgeListToCOO,
+// :314-391 WriteCSRToMTX / WriteCOOToMTX / WriteArrayToMTX); the text files are parsed and formatted on the GPU.
+// Binary (SbFF) facade: :195-295.
+// Divergences: WriteCOOToMTX takes a COO* (the reference declares CSR* there and hands it to WriteCOO: the template
+// cannot be instantiated); the three MTX writers take the writer's `precision` as one more, last argument.
 #ifndef SPARSEBASE_BASES_IOBASE_H_
 #define SPARSEBASE_BASES_IOBASE_H_
 #include "sparsebase/io/binary_reader_order_one.h"
@@ -25,6 +28,11 @@ class IOBase {
   static format::COO<IDType, NNZType, ValueType> *ReadMTXToCOO(std::string filename, bool convert_index_to_zero = true) {
     io::MTXReader<IDType, NNZType, ValueType> reader(filename, convert_index_to_zero);
     return reader.ReadCOO();
+  }
+  template <typename IDType, typename NNZType, typename ValueType>
+  static format::Array<ValueType> *ReadMTXToArray(std::string filename, bool convert_index_to_zero = true) {
+    io::MTXReader<IDType, NNZType, ValueType> reader(filename, convert_index_to_zero);
+    return reader.ReadArray();
   }
   // like the reference, the facade always removes duplicate edges (iobase.h:165-166)
   template <typename IDType, typename NNZType, typename ValueType>
@@ -64,6 +72,25 @@ class IOBase {
   template <typename ValueType>
   static void WriteArrayToBinary(format::Array<ValueType> *array, std::string filename) {
     io::BinaryWriterOrderOne<ValueType>(filename).WriteArray(array);
+  }
+  // the reference's defaults, "coordinate" for an Array included (which MTXWriter::WriteArray refuses, there as here)
+  template <typename IDType, typename NNZType, typename ValueType>
+  static void WriteCSRToMTX(format::CSR<IDType, NNZType, ValueType> *csr, std::string filename, std::string object = "matrix",
+                            std::string format = "coordinate", std::string field = "real",
+                            std::string symmetry = "general", int precision = 6) {
+    io::MTXWriter<IDType, NNZType, ValueType>(filename, object, format, field, symmetry, precision).WriteCSR(csr);
+  }
+  template <typename IDType, typename NNZType, typename ValueType>
+  static void WriteCOOToMTX(format::COO<IDType, NNZType, ValueType> *coo, std::string filename, std::string object = "matrix",
+                            std::string format = "coordinate", std::string field = "real",
+                            std::string symmetry = "general", int precision = 6) {
+    io::MTXWriter<IDType, NNZType, ValueType>(filename, object, format, field, symmetry, precision).WriteCOO(coo);
+  }
+  template <typename IDType, typename NNZType, typename ValueType>
+  static void WriteArrayToMTX(format::Array<ValueType> *arr, std::string filename, std::string object = "matrix",
+                              std::string format = "coordinate", std::string field = "real",
+                              std::string symmetry = "general", int precision = 6) {
+    io::MTXWriter<IDType, NNZType, ValueType>(filename, object, format, field, symmetry, precision).WriteArray(arr);
   }
 };
 

@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -210,6 +210,45 @@ def mtx_parse_coordinate(text, n_rows, n_cols, entries, fields, symmetry=0, zero
                                              fields, symmetry, flags, cap, _p(row), _p(col), _p(val), C.byref(nnz)))
     k = nnz.value
     return row[:k], col[:k], (None if val is None else val[:k])
+
+
+def mtx_parse_values(text, count, value_dtype):
+    """text: uint8 device tensor with the bytes after the size line of an array-format file.  Returns its first `count`
+    values, in file order (sbio_mtx_parse_values)."""
+    hd = handle_for(_check_dev(text))
+    val = torch.empty(max(1, count), dtype=value_dtype, device=text.device)
+    hd.check(hd.lib.sbio_mtx_parse_values(hd.h, _vt(val), _p(text), text.numel(), count, _p(val)))
+    return val[:count]
+
+
+def dense_to_coo(n, m, dense, index_dtype=torch.int32):
+    """dense: n * m values in column-major order (cell (r, c) at c * n + r).  Returns (row, col, val) of the cells with
+    value != 0, ordered by (row, col), trimmed to nnz (sbio_dense_to_coo: the counting call, the allocation, the fill)."""
+    dev = _check_dev(dense)
+    hd = handle_for(dev)
+    if dense.numel() != n * m:
+        raise ValueError(f"dense holds {dense.numel()} values, {n} x {m} needs {n * m}")
+    it = _it(torch.empty(0, dtype=index_dtype))
+    nnz = C.c_int64(0)
+    hd.check(hd.lib.sbio_dense_to_coo(hd.h, it, _vt(dense), n, m, _p(dense), 0, None, None, None, C.byref(nnz)))
+    k = nnz.value
+    row = torch.empty(k, dtype=index_dtype, device=dev)
+    col = torch.empty(k, dtype=index_dtype, device=dev)
+    val = torch.empty(k, dtype=dense.dtype, device=dev)
+    if k:
+        hd.check(hd.lib.sbio_dense_to_coo(hd.h, it, _vt(dense), n, m, _p(dense), k, _p(row), _p(col), _p(val), C.byref(nnz)))
+        assert nnz.value == k
+    return row, col, val
+
+
+def coo_to_dense_vector(length, row, col, val):
+    """The dense vector of a sorted COO of a 1 x N or N x 1 matrix: zeros, then out[row + col] = val, the last of equal
+    positions winning (sbio_coo_to_dense_vector)."""
+    dev = _check_dev(row, col, val)
+    hd = handle_for(dev)
+    out = torch.empty(length, dtype=val.dtype, device=dev)
+    hd.check(hd.lib.sbio_coo_to_dense_vector(hd.h, _it(row), _vt(val), length, row.numel(), _p(row), _p(col), _p(val), _p(out)))
+    return out
 
 
 def text_count_tokens(text):
