@@ -69,8 +69,8 @@ struct RcmDev {
   alignas(128) unsigned n_heavy;             // hub chunk descriptors queued for the chunked kernel
   unsigned hub_overflow;                     // some workgroup reserved descriptors outside its directory entry
   alignas(128) unsigned long long fedges;    // sum of degrees of the level being built (direction heuristic)
-  alignas(128) unsigned long long edges;     // adjacency entries scanned (statistics)
-  alignas(128) unsigned long long edges_bu;  // adjacency entries scanned by the bottom-up kernel
+  alignas(128) unsigned long long edges;     // adjacency entries scanned by everything but the bottom-up kernels (statistics)
+  alignas(128) unsigned long long edges_bu;  // adjacency entries scanned by the bottom-up kernels
   alignas(128) unsigned n_small;             // small components listed
   unsigned n_large;             // large components listed
   unsigned n_mid;               // components of RCM_SMALL + 1 .. RCM_MID vertices listed
@@ -640,14 +640,16 @@ __device__ __forceinline__ void stage_flush(WaveStage &st, I *__restrict__ nf_li
   st.cnt = 0;
 }
 
-// Kernel epilogue for a 256-thread workgroup: what is still staged is appended with one
+// Kernel epilogue for a workgroup of NW waves: what is still staged is appended with one
 // returning atomic per workgroup, and the degree / edge counters get one atomic each
 // (8192 waves x 3 atomics on one cache line cost more than a small level's expansion).
+// The entries a bottom-up kernel scanned count in edges_bu alone: the host reports edges + edges_bu.
 // `scanned` is a per-lane partial.  Every thread of the workgroup must call it.
+template <int NW = 4>
 __device__ __forceinline__ void stage_end_block(WaveStage &st, I *__restrict__ nf_list, RcmDev *__restrict__ dv,
                                                 unsigned long long scanned, bool bottom_up) {
-  __shared__ unsigned s_cnt[4];
-  __shared__ unsigned long long s_deg[4], s_scan[4];
+  __shared__ unsigned s_cnt[NW];
+  __shared__ unsigned long long s_deg[NW], s_scan[NW];
   __shared__ unsigned s_base;
   const int w = sbx_wave_in_block();
   const unsigned long long d = sbx_wave_sum(st.deg);
@@ -659,15 +661,18 @@ __device__ __forceinline__ void stage_end_block(WaveStage &st, I *__restrict__ n
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    const unsigned long long dsum = s_deg[0] + s_deg[1] + s_deg[2] + s_deg[3];
-    const unsigned long long ssum = s_scan[0] + s_scan[1] + s_scan[2] + s_scan[3];
+    unsigned tot = 0;
+    unsigned long long dsum = 0, ssum = 0;
+    if constexpr (NW <= 4) {
+#pragma unroll
+      for (int q = 0; q < NW; q++) tot += s_cnt[q], dsum += s_deg[q], ssum += s_scan[q];
+    } else {
+#pragma nounroll  // (unrolled, sixteen waves' words are all in registers at once and the bottom-up kernels spill)
+      for (int q = 0; q < NW; q++) tot += s_cnt[q], dsum += s_deg[q], ssum += s_scan[q];
+    }
     s_base = tot ? atomicAdd(st.nf_ctr, tot) : 0u;
     if (dsum) atomicAdd(st.fe_ctr, dsum);
-    if (ssum) {
-      atomicAdd(&dv->edges, ssum);
-      if (bottom_up) atomicAdd(&dv->edges_bu, ssum);
-    }
+    if (ssum) atomicAdd(bottom_up ? &dv->edges_bu : &dv->edges, ssum);
   }
   __syncthreads();
   unsigned base = s_base;
@@ -986,12 +991,25 @@ constexpr int RCM_BU_B = SBX_RCM_BU_B;
 constexpr int RCM_BU_LANE_BITS = RCM_BU_B * 32 / 64;  // bits of a block a lane compacts
 static_assert(RCM_BU_B >= 2 && RCM_BU_B <= 64 && 32 % RCM_BU_LANE_BITS == 0, "a lane's bits lie in one word of the block");
 typedef unsigned short BuOff;  // a candidate's offset in its block (< 2048)
-// (LDS of a workgroup of the kernels below: the stage, the lists and the block's words.  Their grids are eight workgroups
-// per CU, resident together — see the launch bounds — so eight of them must fit the 160 KB of a gfx950 CU.  Up to
-// B = 32 they do: 17 KB each.  A B = 64 variant takes 25 KB, six per CU — part of what its first levels measured.)
-static_assert(RCM_BU_B > 32 || 8 * (4 * RCM_STAGE * sizeof(I) + 4 * RCM_BU_B * 32 * sizeof(BuOff) +
-                                    4 * RCM_BU_B * sizeof(unsigned) + 128) <= 160 * 1024,
-              "eight workgroups of the block kernels per CU");
+// The four kernels of a bottom-up level (with and without the block front end, ordered and unordered) run as workgroups
+// of RCM_BU_WAVES waves, 32 waves per CU — eight per SIMD, every workgroup resident from the start.  What a launch costs
+// when few candidates are left is its epilogue (stage_end_block, ubu_chain_end): adds on a handful of hot words, one per
+// workgroup and word, ~11 ns apiece whoever issues them — 512 workgroups instead of 2048 pay a quarter of it.
+#ifndef SBX_RCM_BU_WAVES
+#define SBX_RCM_BU_WAVES 16  // (a variant build sets it: 4 is the grid of eight 256-thread workgroups per CU)
+#endif
+constexpr int RCM_BU_WAVES = SBX_RCM_BU_WAVES;
+constexpr int RCM_BU_THREADS = 64 * RCM_BU_WAVES;
+constexpr int RCM_BU_WG_PER_CU = 32 / RCM_BU_WAVES;
+static_assert(RCM_BU_WAVES >= 1 && RCM_BU_WAVES <= 16 && 32 % RCM_BU_WAVES == 0, "whole workgroups, 32 waves per CU");
+// LDS of a workgroup of the block kernels: the stage, the list and the block's next-frontier words per wave, and the
+// epilogue's words.  The RCM_BU_WG_PER_CU workgroups that share a CU must fit its 160 KB (gfx950): at sixteen waves
+// B = 32 takes 66 KB (the unordered kernel), two per CU; B = 64 would take 102 KB.  (The 128 bytes stand for s_base and
+// the padding between the arrays; the compiler's figure for B = 32 is 67 912 B against 67 904 + 128 here.)
+static_assert(RCM_BU_WG_PER_CU * (RCM_BU_WAVES * (RCM_STAGE * sizeof(I) + RCM_BU_B * 32 * sizeof(BuOff) +
+                                                  RCM_BU_B * sizeof(unsigned)) +
+                                  RCM_BU_WAVES * (sizeof(unsigned) + 2 * sizeof(unsigned long long)) + 128) <= 160 * 1024,
+              "the workgroups of the block kernels that share a CU do not fit its LDS");
 
 // Front end of a block: loads the block's visited and empty-row words (lane i < RCM_BU_B holds word w0 + i; vw returns the
 // visited word), writes the offsets of the candidates, ascending, to the wave's `list` and returns how many there are
@@ -1124,14 +1142,14 @@ __device__ __forceinline__ void bu_pull64(bool has, int64_t v, const X *__restri
 }
 
 // (eight waves per SIMD: the chunk reservation, which hardly ever runs, would otherwise cost the scans 30 registers)
-__global__ __launch_bounds__(256, 8) void k_bfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
+__global__ __launch_bounds__(RCM_BU_THREADS, 8) void k_bfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
                                                        const I *__restrict__ label, I comp_label,
                                                        const unsigned *__restrict__ vbits,
                                                        const unsigned *__restrict__ fbits,
                                                        const unsigned *__restrict__ lpos, unsigned *__restrict__ ppos,
                                                        I *__restrict__ nf_list, int64_t n, RcmDev *__restrict__ dv,
                                                        uint64_t *__restrict__ heavy, uint64_t heavy_cap) {
-  __shared__ I s_stage[4][RCM_STAGE];
+  __shared__ I s_stage[RCM_BU_WAVES][RCM_STAGE];
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int lane = sbx_lane();
@@ -1142,11 +1160,11 @@ __global__ __launch_bounds__(256, 8) void k_bfs_bottom_up(const X *__restrict__ 
     const bool has = v < n && !((vbits[v >> 5] >> (v & 31)) & 1u);
     bu_pull64(has, v, rp, col, label, comp_label, fbits, lpos, ppos, nf_list, dv, heavy, heavy_cap, st, scanned);
   }
-  stage_end_block(st, nf_list, dv, scanned, true);
+  stage_end_block<RCM_BU_WAVES>(st, nf_list, dv, scanned, true);
 }
 
 // the same level with the block front end (see above): the candidates come off the bitmaps
-__global__ __launch_bounds__(256, 8) void k_bfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
+__global__ __launch_bounds__(RCM_BU_THREADS, 8) void k_bfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
                                                               const I *__restrict__ label, I comp_label,
                                                               const unsigned *__restrict__ vbits,
                                                               const unsigned *__restrict__ ebits,
@@ -1154,11 +1172,11 @@ __global__ __launch_bounds__(256, 8) void k_bfs_bottom_up_blocks(const X *__rest
                                                               const unsigned *__restrict__ lpos, unsigned *__restrict__ ppos,
                                                               I *__restrict__ nf_list, int64_t n, RcmDev *__restrict__ dv,
                                                               uint64_t *__restrict__ heavy, uint64_t heavy_cap) {
-  __shared__ I s_stage[4][RCM_STAGE];
-  __shared__ BuOff s_list[4][RCM_BU_B * 32];
+  __shared__ I s_stage[RCM_BU_WAVES][RCM_STAGE];
+  __shared__ BuOff s_list[RCM_BU_WAVES][RCM_BU_B * 32];
   // (the wave's number in a scalar register: the block loop and the LDS slices then cost no vector registers)
   const int wv = __builtin_amdgcn_readfirstlane(sbx_wave_in_block());
-  const int64_t wave = (int64_t)blockIdx.x * 4 + wv, nwaves = (int64_t)gridDim.x * 4;
+  const int64_t wave = (int64_t)blockIdx.x * RCM_BU_WAVES + wv, nwaves = (int64_t)gridDim.x * RCM_BU_WAVES;
   const int lane = sbx_lane();
   BuOff *list = s_list[wv];
   WaveStage st{s_stage[wv], 0u, 0ull, &dv->nf, &dv->fedges};
@@ -1173,7 +1191,7 @@ __global__ __launch_bounds__(256, 8) void k_bfs_bottom_up_blocks(const X *__rest
       bu_pull64(has, v, rp, col, label, comp_label, fbits, lpos, ppos, nf_list, dv, heavy, heavy_cap, st, scanned);
     }
   }
-  stage_end_block(st, nf_list, dv, scanned, true);
+  stage_end_block<RCM_BU_WAVES>(st, nf_list, dv, scanned, true);
 }
 
 // The queued row chunks of a bottom-up level: a wave scans the RCM_BU_CHUNK entries of one (four loads per lane in
@@ -2097,6 +2115,9 @@ struct BfsBuffers {
   bool *last_read_joined;
 };
 
+// the grid of a bottom-up level: 32 waves per CU, all resident (see RCM_BU_WAVES)
+static unsigned bu_grid(sbx_handle_t h) { return (unsigned)h->num_cus * (unsigned)RCM_BU_WG_PER_CU; }
+
 // cover_us: roughly how long the kernels just enqueued keep the GPU busy before the host's next read-back returns
 static int bfs_first_launch(const BfsBuffers &b, int cover_us = 1000) {  // (the hook ignores every call after its last stage)
   if (!b.after_first_launch) return SBX_OK;
@@ -2188,13 +2209,13 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
                     (const I *)(b.q + off), fsize, b.fbits, b.lpos);
       }
       if (sbx_sw().rcm_bu_blocks)
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_blocks, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                    (const unsigned *)b.vbits, (const unsigned *)b.ebits, (const unsigned *)b.fbits, (const unsigned *)b.lpos,
-                    b.ppos, b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col,
+                    b.label, comp_label, (const unsigned *)b.vbits, (const unsigned *)b.ebits,
+                    (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
       else
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(max_grid), dim3(256), b.rp, b.col, b.label, comp_label,
-                    (const unsigned *)b.vbits, (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list,
-                    b.n, b.dv, b.heavy, b.heavy_cap);
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col, b.label,
+                    comp_label, (const unsigned *)b.vbits, (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos,
+                    b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
       if (b.max_deg > (unsigned)RCM_BU_HEAVY)
         SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_heavy, dim3(8 * (unsigned)h->num_cus), dim3(256), b.rp, b.col,
                     (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list, b.dv,
@@ -2633,7 +2654,7 @@ __device__ __forceinline__ void ubu_chain_end(RcmDev *dv, int chain, const Chain
   if (chain && threadIdx.x == 0) {
     // This workgroup's additions to the level's counters were returning atomics or thread 0's own: waiting for the
     // latter is all the ordering the election needs (the counters live in L2 and are read there).  A release fence
-    // here — a write-back of the L2 per workgroup, 2048 of them — doubled the kernel's time.
+    // here — a write-back of the L2 per workgroup, 2048 of them then — doubled the kernel's time.
     // Words under the invariant (see gb_wait): the level's counters unf[] / ufedges[] / n_heavy (returning atomics of the
     // waves, or thread 0's own adds), uc_done (the election), and what uc_advance / uc_begin write for the next link
     // of the chain (uc_mode, uc_level, uc_off, ...: read by kernels launched behind this one, i.e. behind a kernel boundary).
@@ -2649,7 +2670,7 @@ __device__ __forceinline__ void ubu_chain_end(RcmDev *dv, int chain, const Chain
   }
 }
 
-__global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
+__global__ __launch_bounds__(RCM_BU_THREADS, 8) void k_ubfs_bottom_up(const X *__restrict__ rp, const X *__restrict__ col,
                                                         const I *__restrict__ label, I comp_label,
                                                         unsigned *vbits, const unsigned *__restrict__ fbits,
                                                         unsigned *__restrict__ nbits, unsigned *__restrict__ dist,
@@ -2663,7 +2684,7 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
     level = dv->uc_level + 1;
     nf_list += dv->uc_off + dv->uc_size;
   }
-  __shared__ I s_stage[4][RCM_STAGE];
+  __shared__ I s_stage[RCM_BU_WAVES][RCM_STAGE];
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int lane = sbx_lane();
@@ -2690,7 +2711,7 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
       if (wbits) vbits[(base >> 5) + (lane >> 5)] |= wbits;
     }
   }
-  stage_end_block(st, nf_list, dv, scanned, true);
+  stage_end_block<RCM_BU_WAVES>(st, nf_list, dv, scanned, true);
   ubu_chain_end(dv, chain, ci);
 }
 
@@ -2698,9 +2719,9 @@ __global__ __launch_bounds__(256) void k_ubfs_bottom_up(const X *__restrict__ rp
 // publishes them as the kernel above does — the found candidates OR their bit into a copy of the block's next-frontier
 // words in LDS, and when the block is done lane i writes word i: nbits always (every word below ceil(n / 32) is written,
 // also those of a block without candidates; no reader looks past vertex n - 1), vbits where something was found
-// (eight waves per SIMD, as k_bfs_bottom_up: the grid is eight workgroups per CU and a wave has one block or two — a
+// (eight waves per SIMD, as k_bfs_bottom_up: the grid is 32 waves per CU and a wave has one block or two — a
 // workgroup that had to wait for a place would double the level's time)
-__global__ __launch_bounds__(256, 8) void k_ubfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
+__global__ __launch_bounds__(RCM_BU_THREADS, 8) void k_ubfs_bottom_up_blocks(const X *__restrict__ rp, const X *__restrict__ col,
                                                                const I *__restrict__ label, I comp_label,
                                                                unsigned *vbits, const unsigned *__restrict__ ebits,
                                                                const unsigned *__restrict__ fbits,
@@ -2712,11 +2733,11 @@ __global__ __launch_bounds__(256, 8) void k_ubfs_bottom_up_blocks(const X *__res
     level = dv->uc_level + 1;
     nf_list += dv->uc_off + dv->uc_size;
   }
-  __shared__ I s_stage[4][RCM_STAGE];
-  __shared__ BuOff s_list[4][RCM_BU_B * 32];
-  __shared__ unsigned s_next[4][RCM_BU_B];
+  __shared__ I s_stage[RCM_BU_WAVES][RCM_STAGE];
+  __shared__ BuOff s_list[RCM_BU_WAVES][RCM_BU_B * 32];
+  __shared__ unsigned s_next[RCM_BU_WAVES][RCM_BU_B];
   const int wv = __builtin_amdgcn_readfirstlane(sbx_wave_in_block());
-  const int64_t wave = (int64_t)blockIdx.x * 4 + wv, nwaves = (int64_t)gridDim.x * 4;
+  const int64_t wave = (int64_t)blockIdx.x * RCM_BU_WAVES + wv, nwaves = (int64_t)gridDim.x * RCM_BU_WAVES;
   const int lane = sbx_lane();
   BuOff *list = s_list[wv];
   unsigned *next = s_next[wv];
@@ -2754,7 +2775,7 @@ __global__ __launch_bounds__(256, 8) void k_ubfs_bottom_up_blocks(const X *__res
       if (wbits) vbits[w0 + lane] = vw | wbits;
     }
   }
-  stage_end_block(st, nf_list, dv, scanned, true);
+  stage_end_block<RCM_BU_WAVES>(st, nf_list, dv, scanned, true);
   ubu_chain_end(dv, chain, ci);
 }
 
@@ -3860,14 +3881,14 @@ __global__ __launch_bounds__(256) void k_check_closed(const X *__restrict__ rp, 
 }
 
 // one unordered bottom-up level: the kernel with the block front end, or (SBX_RCM_BU_BLOCKS=0) the one with a lane per vertex
-static void launch_ubfs_bottom_up(sbx_handle_t h, const BfsBuffers &b, unsigned grid, I comp_label, const unsigned *cur_f,
+static void launch_ubfs_bottom_up(sbx_handle_t h, const BfsBuffers &b, I comp_label, const unsigned *cur_f,
                                   unsigned *cur_n, unsigned *dist, unsigned level, I *nf_list, int chain, const ChainInit &ci) {
   if (sbx_sw().rcm_bu_blocks)
-    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up_blocks, dim3(grid), dim3(256), b.rp, b.col, b.label, comp_label, b.vbits,
-                b.ebits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col,
+                b.label, comp_label, b.vbits, b.ebits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
   else
-    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(grid), dim3(256), b.rp, b.col, b.label, comp_label, b.vbits,
-                cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col, b.label,
+                comp_label, b.vbits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
 }
 
 // One unordered sweep from fixed_root (>= 0) or dv->root: level sets only.  *too_deep is set when the sweep passed the
@@ -3934,7 +3955,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
                     (const unsigned *)b.vbits, (const unsigned *)dist, 0u, b.n, cur_f, (const RcmDev *)b.dv);
         unsigned *cf = cur_f, *cn = cur_n;
         for (int i = 0; i <= spec_len; i++) {
-          launch_ubfs_bottom_up(h, b, max_grid, comp_label, cf, cn, dist, 0u, b.q, 1, ci0);
+          launch_ubfs_bottom_up(h, b, comp_label, cf, cn, dist, 0u, b.q, 1, ci0);
           std::swap(cf, cn);
         }
         SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
@@ -4015,7 +4036,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
                     (const unsigned *)b.vbits, (const unsigned *)dist, level, b.n, cur_f, (const RcmDev *)nullptr);
       // publishes the level itself (bitmaps, distances, queue): no collection pass
-      launch_ubfs_bottom_up(h, b, max_grid, comp_label, cur_f, cur_n, dist, level + 1, q_next, chain_len > 0 ? 2 : 0, ci);
+      launch_ubfs_bottom_up(h, b, comp_label, cur_f, cur_n, dist, level + 1, q_next, chain_len > 0 ? 2 : 0, ci);
       std::swap(cur_f, cur_n);
     } else {
       const unsigned waves_needed = (fsize + RCM_VPW - 1) / RCM_VPW;
@@ -4042,7 +4063,7 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
       // A sweep of the bench matrix: a small run, three bottom-up levels, a small run — five round trips, now two.
       unsigned *cf = cur_f, *cn = cur_n;
       for (int i = 0; i < chain_len; i++) {
-        launch_ubfs_bottom_up(h, b, max_grid, comp_label, cf, cn, dist, 0u, b.q, 1, ci);
+        launch_ubfs_bottom_up(h, b, comp_label, cf, cn, dist, 0u, b.q, 1, ci);
         std::swap(cf, cn);
       }
       SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
@@ -4802,7 +4823,7 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
     stats_host->large_components = n_host;
     stats_host->bfs_sweeps = sweeps_max;
     stats_host->bfs_levels = levels_max;
-    stats_host->edges_scanned = (int64_t)fin.edges;
+    stats_host->edges_scanned = (int64_t)(fin.edges + fin.edges_bu);  // (a bottom-up kernel counts in edges_bu alone)
     stats_host->edges_scanned_bottom_up = (int64_t)fin.edges_bu;
     stats_host->largest_component = largest;
     stats_host->components = (int64_t)hd.n_components;
