@@ -31,6 +31,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbx_text.h"))
     hs.append(os.path.join(ROOT, "include", "sbx_stats.h"))
     hs.append(os.path.join(ROOT, "include", "sbio.h"))
+    hs.append(os.path.join(ROOT, "include", "sbgr.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h and include/sbio.h
+"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h and include/sbgr.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -20,6 +20,7 @@ TC_DIRECTED, TC_EXACT = 1, 2
 SB_GREEDY, SB_HUB_ORDER = 1, 2
 TEXT_LOWER, TEXT_NO_DIAGONAL, TEXT_PATTERN = 1, 2, 4
 STAT_MEDIAN, STAT_LOG = 1, 2
+GR_ZERO_INDEX, GR_EDGE_WEIGHTS, GR_VERTEX_WEIGHTS = 1, 2, 4
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -151,6 +152,15 @@ IO_PROTOTYPES = {
     "sbio_coo_to_dense_vector": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp], _int),
 }
 
+# every symbol include/sbgr.h declares (tests/test_graph_abi.py checks header <-> library <-> this table): the METIS graph
+# format, prefix `sbgr_`
+GRAPH_PROTOTYPES = {
+    "sbgr_metis_parse": ([_H, _int, _int, _vp, _i64, _i64, _i64, _int, _int, _u, _i64, _vp, _vp, _vp, _vp, _vp,
+                          C.POINTER(_i64)], _int),
+    "sbgr_metis_format": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i64, _int, _u, _vp, _i64,
+                           C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -163,7 +173,8 @@ def load():
                               "(there is no CPU fallback for the HIP hot path)")
         lib = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
-                                           list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items())):
+                                           list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
+                                           list(GRAPH_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -34,25 +34,9 @@ __global__ __launch_bounds__(MX_THREADS) void k_dense_parse(const char *__restri
   const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= count) return;
   unsigned bad = 0;
-  uint64_t vbits = 0;
   const int64_t s = tok_off[l];
-  const int64_t len = mx_token_len(text, bytes, s);
-  if (VKIND == 1) {
-    long long v = 0;
-    if (sbx_parse_integer(text + s, len, &v)) bad |= DN_BAD_VALUE;
-    if (VB == 4) {
-      if (value_signed ? (v < -2147483648ll || v > 2147483647ll) : (v < 0 || v > 4294967295ll)) bad |= DN_BAD_VALUE;
-    } else if (!value_signed && v < 0) {
-      bad |= DN_BAD_VALUE;
-    }
-    vbits = (uint64_t)v;
-  } else {
-    const sbx_decimal d = sbx_parse_decimal(text + s, len);
-    if (d.status == 1) bad |= DN_BAD_VALUE;
-    if (d.status == 2) bad |= DN_TOO_MANY_DIGITS;
-    if (VKIND == 2) vbits = (uint64_t)(sbx_decimal_to_float_bits(d, pow5) | ((uint32_t)d.neg << 31));
-    else vbits = sbx_decimal_to_double_bits(d, pow5) | ((uint64_t)d.neg << 63);
-  }
+  static_assert(DN_BAD_VALUE == MX_VALUE_BAD && DN_TOO_MANY_DIGITS == MX_VALUE_DIGITS, "the status bits of mx_parse_value");
+  const uint64_t vbits = mx_parse_value<VKIND, VB>(text + s, mx_token_len(text, bytes, s), value_signed, pow5, &bad);
   if (VB == 4) ((uint32_t *)val)[l] = (uint32_t)vbits;
   else ((uint64_t *)val)[l] = vbits;
   if (bad) atomicOr(status, bad);

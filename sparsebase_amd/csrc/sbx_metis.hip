@@ -1,0 +1,604 @@
+// sbx_metis.hip — the METIS graph format on the device (include/sbgr.h).
+//
+//   io/metis_graph_reader.cc:42-101   the vertex lines of MetisGraphReader::ReadGraph    sbgr_metis_parse
+//   io/metis_graph_writer.cc:45-82    the vertex lines of MetisGraphWriter::WriteGraph   sbgr_metis_format
+//
+// The reference reads with getline and one istringstream per line.  The format is the one text format here whose lines
+// carry structure — line k is vertex k — but a hub vertex puts a million neighbours on one line, so the work is per token
+// and per line start, never a walk along a line:
+//   1. line starts (byte 0 and every byte behind a '\n') and token starts (sbx_mtx_tokens.h) are counted per 4096-byte
+//      tile and compacted in file order: two ascending offset arrays;
+//   2. k_gr_lines    one thread per line: the index of its first token (a search in the token starts), from that and the
+//                    next line's the number of its tokens and of its entries, and whether it is a comment; two scans over
+//                    the lines give every line its first entry and its vertex;
+//   3. k_gr_tokens   one thread per token: its line (a search in the line starts), its ordinal in the line and from that
+//                    its role — vertex weight, neighbour, edge weight — and the slot it fills; parsed as the coordinate
+//                    parser parses (sbx_dec2bin.h, exact);
+//   4. the entries are grouped by row already: the row offsets are the scan of step 2, and only if some row is out of
+//      order (sbx_csr_rows_sorted) its inside is sorted, stably (sbx_sort_segments).
+// The writer is a formatter of sbx_text.hip's kind over ITEMS — per row one head (the '\n' of the row before), its vertex
+// weights, its entries, and one last '\n' — whose lengths are summed per workgroup, scanned, and written through LDS.
+#include "sbgr.h"
+#include "sbx_dec2bin.h"
+#include "sbx_device.h"
+#include "sbx_internal.h"
+#include "sbx_mtx_tokens.h"
+#include "sbx_text_emit.h"
+
+namespace {
+
+enum : unsigned { GR_BAD_ID = 1u, GR_BAD_VALUE = 2u, GR_TOO_MANY_DIGITS = 4u, GR_ID_RANGE = 8u, GR_ODD_LINE = 16u };
+
+// ---- line starts: byte 0 and every byte behind a '\n' (a '\n' that ends the text starts nothing)
+__device__ __forceinline__ unsigned gr_line_starts(const char *__restrict__ text, int64_t bytes, int64_t p0) {
+  static_assert(MX_BPT == 16, "one 16-byte load per thread");
+  unsigned mask = 0;
+  bool prev_nl = p0 == 0 || text[p0 - 1] == '\n';
+  if (p0 + MX_BPT <= bytes && (((uintptr_t)text + (uintptr_t)p0) & 15) == 0) {
+    const uint4 v = *(const uint4 *)(text + p0);
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < MX_BPT; k++) {
+      if (prev_nl) mask |= 1u << k;
+      prev_nl = (char)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) == '\n';
+    }
+    return mask;
+  }
+#pragma unroll
+  for (int k = 0; k < MX_BPT; k++) {
+    if (p0 + k >= bytes) break;
+    if (prev_nl) mask |= 1u << k;
+    prev_nl = text[p0 + k] == '\n';
+  }
+  return mask;
+}
+
+__global__ __launch_bounds__(MX_THREADS) void k_gr_line_count(const char *__restrict__ text, int64_t bytes,
+                                                              unsigned *__restrict__ tile_lines) {
+  __shared__ unsigned s_red[MX_THREADS / 64 + 1];
+  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
+  const unsigned c = p0 < bytes ? (unsigned)__popc(gr_line_starts(text, bytes, p0)) : 0u;
+  const unsigned tot = sbx_block_sum<unsigned, MX_THREADS>(c, s_red);
+  if (threadIdx.x == 0) tile_lines[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(MX_THREADS) void k_gr_line_offsets(const char *__restrict__ text, int64_t bytes,
+                                                                const unsigned *__restrict__ tile_base, int64_t lines,
+                                                                unsigned *__restrict__ line_off) {
+  __shared__ unsigned s_scan[MX_THREADS / 64 + 1];
+  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
+  unsigned mask = p0 < bytes ? gr_line_starts(text, bytes, p0) : 0u;
+  unsigned all;
+  unsigned t = tile_base[blockIdx.x] + sbx_block_exclusive_sum<unsigned, MX_THREADS>((unsigned)__popc(mask), s_scan, &all);
+  while (mask) {
+    const int k = __ffs(mask) - 1;
+    mask &= mask - 1;
+    if ((int64_t)t < lines) line_off[t] = (unsigned)(p0 + k);
+    t++;
+  }
+}
+
+// first index i in [0, len) with arr[i] >= target, or len
+__device__ __forceinline__ int64_t gr_lower_bound(const unsigned *__restrict__ arr, int64_t len, unsigned target) {
+  int64_t lo = 0, hi = len;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (arr[mid] < target) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// one thread per line, and one for the end of the arrays: first token, entries, comment or not
+__global__ __launch_bounds__(MX_THREADS) void k_gr_lines(const char *__restrict__ text, const unsigned *__restrict__ line_off,
+                                                         int64_t lines, const unsigned *__restrict__ tok_off, int64_t tokens,
+                                                         int nvw, int edge_weighted, unsigned *__restrict__ line_tok,
+                                                         unsigned *__restrict__ line_cnt, unsigned *__restrict__ line_nc,
+                                                         unsigned *__restrict__ status) {
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l > lines) return;
+  if (l == lines) {
+    line_tok[l] = (unsigned)tokens;
+    line_cnt[l] = 0;
+    line_nc[l] = 0;
+    return;
+  }
+  const unsigned start = line_off[l];
+  const int64_t a = gr_lower_bound(tok_off, tokens, start);
+  const int64_t b = l + 1 < lines ? gr_lower_bound(tok_off, tokens, line_off[l + 1]) : tokens;
+  const bool comment = text[start] == '%';
+  int64_t k = b - a - nvw;  // neighbour (and edge weight) tokens
+  if (k < 0) k = 0;
+  if (!comment && edge_weighted && (k & 1)) atomicOr(status, GR_ODD_LINE);
+  line_tok[l] = (unsigned)a;
+  line_cnt[l] = comment ? 0u : (unsigned)(edge_weighted ? k >> 1 : k);
+  line_nc[l] = comment ? 0u : 1u;
+}
+
+// row offsets: the row of the j-th line that is no comment begins at that line's first entry ...
+__global__ __launch_bounds__(MX_THREADS) void k_gr_row_ptr_lines(const unsigned *__restrict__ line_ent,
+                                                                 const unsigned *__restrict__ line_ncb, int64_t lines, int base,
+                                                                 int32_t *__restrict__ rp) {
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= lines || line_ncb[l + 1] == line_ncb[l]) return;
+  rp[(int64_t)line_ncb[l] + base] = (int32_t)line_ent[l];
+}
+// ... row 0 of a 1-based graph at 0, and the rows without a line (and the end) at nnz
+__global__ __launch_bounds__(MX_THREADS) void k_gr_row_ptr_rest(int64_t n_dim, int base, int64_t vertex_lines, int32_t nnz,
+                                                                int32_t *__restrict__ rp) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > n_dim) return;
+  if (r < base) rp[r] = 0;
+  else if (r >= vertex_lines + base) rp[r] = nnz;
+}
+
+template <int VB>
+__device__ __forceinline__ void gr_store_value(char *__restrict__ dst, int64_t i, uint64_t bits) {
+  if (VB == 4) ((uint32_t *)dst)[i] = (uint32_t)bits;
+  else ((uint64_t *)dst)[i] = bits;
+}
+
+// one thread per token
+template <int VKIND /*0 none, 1 integer, 2 float, 3 double*/, int VB>
+__global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict__ text, int64_t bytes,
+                                                          const unsigned *__restrict__ tok_off, int64_t tokens,
+                                                          const unsigned *__restrict__ line_off, int64_t lines,
+                                                          const unsigned *__restrict__ line_tok,
+                                                          const unsigned *__restrict__ line_ent,
+                                                          const unsigned *__restrict__ line_ncb, int nvw, int ncon,
+                                                          int edge_weighted, int zero_index, int64_t n_dim, int64_t nnz,
+                                                          int value_signed, const uint64_t *__restrict__ pow5,
+                                                          int32_t *__restrict__ row, int32_t *__restrict__ col,
+                                                          char *__restrict__ val, char *__restrict__ vwgt,
+                                                          unsigned *__restrict__ status) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= tokens) return;
+  const unsigned s = tok_off[t];
+  const int64_t l = gr_lower_bound(line_off, lines, s + 1u) - 1;  // the last line that starts at or before the token
+  if (l < 0 || line_ncb[l + 1] == line_ncb[l]) return;            // (a token of a comment line does not exist)
+  const int64_t vertex = (int64_t)line_ncb[l] + (zero_index ? 0 : 1);
+  const int64_t ord = t - (int64_t)line_tok[l];
+  const int64_t len = mx_token_len(text, bytes, s);
+  unsigned bad = 0;
+  if (ord < nvw) {  // a vertex weight
+    if (VKIND != 0 && vwgt) {
+      unsigned vf = 0;
+      const uint64_t bits = mx_parse_value<VKIND == 0 ? 1 : VKIND, VB>(text + s, len, value_signed, pow5, &vf);
+      if (vf & MX_VALUE_BAD) bad |= GR_BAD_VALUE;
+      if (vf & MX_VALUE_DIGITS) bad |= GR_TOO_MANY_DIGITS;
+      gr_store_value<VB>(vwgt, vertex * ncon + ord, bits);
+    }
+  } else {
+    const int64_t k = ord - nvw;
+    const int64_t pos = (int64_t)line_ent[l] + (edge_weighted ? k >> 1 : k);
+    if (pos < nnz) {  // (always, once the host has compared the counts)
+      if (edge_weighted && (k & 1)) {
+        if (VKIND != 0 && val) {
+          unsigned vf = 0;
+          const uint64_t bits = mx_parse_value<VKIND == 0 ? 1 : VKIND, VB>(text + s, len, value_signed, pow5, &vf);
+          if (vf & MX_VALUE_BAD) bad |= GR_BAD_VALUE;
+          if (vf & MX_VALUE_DIGITS) bad |= GR_TOO_MANY_DIGITS;
+          gr_store_value<VB>(val, pos, bits);
+        }
+      } else {
+        long long id = 0;
+        if (sbx_parse_integer(text + s, len, &id)) {  // (malformed, not out of range: the message names which)
+          bad |= GR_BAD_ID;
+          id = 0;
+        } else {
+          if (zero_index) id--;
+          if (id < 0 || id >= n_dim) {
+            bad |= GR_ID_RANGE;
+            id = 0;
+          }
+        }
+        row[pos] = (int32_t)vertex;
+        col[pos] = (int32_t)id;
+      }
+    }
+  }
+  if (bad) atomicOr(status, bad);
+}
+
+// ---- the formatter
+enum : int { GV_NONE = 0, GV_SIGNED, GV_UNSIGNED, GV_RECORD };
+
+struct GrJob {
+  const void *rp, *col, *val, *vwgt;
+  const sbx_decrec *rec_val, *rec_vw;  // GV_RECORD: of entry e at [e - e0], of weight j of row r at [(r - rb) * ncon + j]
+  int64_t rb, re, e0, items, base;
+  int nvw, ncon, ew, vw, vkind, vb, precision;
+};
+constexpr int GR_ITEM_MAX = 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 2;  // the longest item: an entry with its value and two blanks
+static_assert(GR_ITEM_MAX <= TX_LINE_MAX && SBX_DEC_MAX_CHARS + 3 <= TX_LINE_MAX, "an item fits its LDS slot");
+
+// Item k of the job.  A row has 1 + nvw + (its entries) items: the head, the vertex weights, the entries; behind the last
+// row comes one item more (the last '\n').  key(r) = the first item of row r; key(re) is that last item.
+template <typename RP>
+__device__ __forceinline__ int64_t gr_key(const GrJob &j, int64_t r) {
+  return ((int64_t)((const RP *)j.rp)[r] - j.e0) + (r - j.rb) * (int64_t)(1 + j.nvw);
+}
+template <typename RP>
+__device__ __forceinline__ void gr_locate(const GrJob &j, int64_t k, int64_t *row, int64_t *sub) {
+  int64_t lo = j.rb, hi = j.re;  // the last row r in [rb, re] with key(r) <= k
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (gr_key<RP>(j, mid) <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  *row = lo;
+  *sub = k - gr_key<RP>(j, lo);
+}
+
+__device__ __forceinline__ int gr_value_length(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel) {
+  if (j.vkind == GV_RECORD) return sbx_b2d::text_length(rec[irel], j.precision);
+  if (j.vkind == GV_SIGNED) return tx_len_signed(j.vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i]);
+  return sbx_b2d::length_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i]);
+}
+__device__ __forceinline__ int gr_value_emit(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel,
+                                             char *dst) {
+  if (j.vkind == GV_RECORD) return sbx_b2d::emit(rec[irel], j.precision, dst);
+  if (j.vkind == GV_SIGNED) return tx_emit_signed(j.vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i], dst);
+  return sbx_b2d::emit_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i], dst);
+}
+
+// the text of item (r, sub): its length; written at dst unless dst is null
+template <typename RP, typename CI>
+__device__ __forceinline__ unsigned gr_item(const GrJob &j, int64_t r, int64_t sub, char *dst) {
+  int o = 0;
+  if (r == j.re) {  // behind the last row
+    if (dst) dst[0] = '\n';
+    return 1;
+  }
+  if (sub == 0) {  // the head: the row before ends; a vertex-weighted row without weights still gets the two blanks
+    if (r > j.rb) {
+      if (dst) dst[o] = '\n';
+      o++;
+    }
+    if (j.vw && j.nvw == 0) {
+      if (dst) dst[o] = ' ', dst[o + 1] = ' ';
+      o += 2;
+    }
+    return (unsigned)o;
+  }
+  if (sub <= j.nvw) {  // vertex weight sub - 1: "w ", and two blanks more behind the last one
+    const int64_t irel = (r - j.rb) * j.ncon + (sub - 1), i = r * j.ncon + (sub - 1);
+    o = dst ? gr_value_emit(j, j.vwgt, j.rec_vw, i, irel, dst) : gr_value_length(j, j.vwgt, j.rec_vw, i, irel);
+    const int blanks = sub == j.nvw ? 3 : 1;
+    if (dst)
+      for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
+    return (unsigned)(o + blanks);
+  }
+  const int64_t e = (int64_t)((const RP *)j.rp)[r] + (sub - 1 - j.nvw);
+  const bool last = e + 1 == (int64_t)((const RP *)j.rp)[r + 1];
+  const int64_t c = (int64_t)((const CI *)j.col)[e] + j.base;
+  if (dst) dst[0] = ' ';
+  o = 1;
+  o += dst ? tx_emit_signed(c, dst + o) : tx_len_signed(c);
+  if (j.ew) {
+    if (dst) dst[o] = ' ';
+    o++;
+    o += dst ? gr_value_emit(j, j.val, j.rec_val, e, e - j.e0, dst + o) : gr_value_length(j, j.val, j.rec_val, e, e - j.e0);
+  }
+  if (!last) {
+    const int blanks = j.ew ? 2 : 1;
+    if (dst)
+      for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
+    o += blanks;
+  }
+  return (unsigned)o;
+}
+
+template <typename RP, typename CI>
+__global__ __launch_bounds__(TX_THREADS) void k_gr_lengths(const GrJob j, int64_t *__restrict__ block_len) {
+  __shared__ unsigned s_red[TX_THREADS / 64 + 1];
+  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  unsigned len = 0;
+  if (k < j.items) {
+    int64_t r, sub;
+    gr_locate<RP>(j, k, &r, &sub);
+    len = gr_item<RP, CI>(j, r, sub, nullptr);
+  }
+  const unsigned tot = sbx_block_sum<unsigned, TX_THREADS>(len, s_red);
+  if (threadIdx.x == 0) block_len[blockIdx.x] = (int64_t)tot;
+}
+
+template <typename RP, typename CI>
+__global__ __launch_bounds__(TX_THREADS) void k_gr_write(const GrJob j, const int64_t *__restrict__ block_off,
+                                                         char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) char s_text[TX_LDS];
+  __shared__ unsigned s_scan[TX_THREADS / 64 + 1];
+  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  unsigned len = 0;
+  int64_t r = 0, sub = 0;
+  if (k < j.items) {
+    gr_locate<RP>(j, k, &r, &sub);
+    len = gr_item<RP, CI>(j, r, sub, nullptr);
+  }
+  unsigned total;
+  const unsigned off = sbx_block_exclusive_sum<unsigned, TX_THREADS>(len, s_scan, &total);
+  char *dst = out + block_off[blockIdx.x];
+  const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
+  if (len) gr_item<RP, CI>(j, r, sub, s_text + phase + off);
+  __syncthreads();
+  tx_block_store(s_text, phase, total, dst);
+}
+
+template <typename T>
+__global__ __launch_bounds__(TX_THREADS) void k_gr_range_ends(const T *__restrict__ rp, int64_t rb, int64_t re,
+                                                              int64_t *__restrict__ ends, unsigned *__restrict__ descending) {
+  // the offsets of the range's ends; whether the offsets of the range descend somewhere
+  const int64_t r = rb + (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  if (r == rb) {
+    ends[0] = (int64_t)rp[rb];
+    ends[1] = (int64_t)rp[re];
+  }
+  if (r < re && rp[r + 1] < rp[r]) atomicOr(descending, 1u);
+}
+
+}  // namespace
+
+#define SBX_REQUIRE(h, cond, msg)                                       \
+  do {                                                                  \
+    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
+  } while (0)
+
+static unsigned gr_grid(int64_t count) { return (unsigned)((count + MX_THREADS - 1) / MX_THREADS); }
+
+extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, const void *text_dev, int64_t bytes,
+                                int64_t n, int64_t m, int fmt, int ncon, unsigned flags, int64_t capacity, void *row_out,
+                                void *col_out, void *val_out, void *vwgt_out, void *row_ptr_out, int64_t *dims_nnz_host) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, dims_nnz_host && bytes >= 0 && (bytes == 0 || text_dev), "bad argument");
+  SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64 || it == SBX_I32_N64, "unknown index type");
+  SBX_REQUIRE(h, n >= 0 && m >= 0 && ncon >= 0 && capacity >= 0, "n, m, ncon and capacity must not be negative");
+  SBX_REQUIRE(h, (flags & ~SBGR_ZERO_INDEX) == 0, "unknown flag");
+  const int vbytes = sbx_value_bytes(vt);
+  SBX_REQUIRE(h, vbytes >= 0, "unknown value type");
+  dims_nnz_host[0] = dims_nnz_host[1] = 0;
+  if (fmt != 0 && fmt != 1 && fmt != 10 && fmt != 11)
+    SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_parse: FMT %d (vertex sizes) is not supported: 0, 1, 10 or 11", fmt);
+  if (bytes >= ((int64_t)1 << 32))
+    SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_parse: texts of 4 GiB and more are not supported (32-bit token offsets)");
+  const bool zero_index = (flags & SBGR_ZERO_INDEX) != 0;
+  const int base = zero_index ? 0 : 1;
+  const int64_t n_dim = n + base;
+  if (n_dim >= ((int64_t)1 << 31) - 1 || m >= ((int64_t)1 << 30))
+    SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_parse: n and 2 * m must be below 2^31");
+  const int64_t nnz = 2 * m;
+  const bool edge_weighted = fmt == 1 || fmt == 11, vertex_weighted = fmt >= 10 && ncon > 0;
+  const int nvw = vertex_weighted ? ncon : 0;
+  SBX_REQUIRE(h, capacity >= nnz, "output capacity: 2 * m entries");
+  SBX_REQUIRE(h, nnz == 0 || (row_out && col_out), "row_out and col_out are needed");
+  char *val = (edge_weighted && vbytes) ? (char *)val_out : nullptr;
+  char *vwgt = (vertex_weighted && vbytes) ? (char *)vwgt_out : nullptr;
+  const bool wide_ids = it == SBX_I64, wide_offsets = it != SBX_I32;
+  SBX_TRY(sbx_arena_begin(h));
+  NestGuard guard(h);
+  const char *text = (const char *)text_dev;
+  const unsigned tiles = (unsigned)((bytes + MX_TILE - 1) / MX_TILE);
+  unsigned *status = nullptr;
+  SBX_TRY(sbx_salloc(h, 1, &status));
+  SBX_HIP(h, hipMemsetAsync(status, 0, sizeof(unsigned), h->stream));
+  // (1) line starts and token starts
+  unsigned lines = 0, tokens = 0;
+  unsigned *tile_lines = nullptr, *tile_tokens = nullptr, *line_off = nullptr, *tok_off = nullptr;
+  if (tiles) {
+    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_lines));
+    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_tokens));
+    SBX_HIP(h, hipMemsetAsync(tile_lines + tiles, 0, sizeof(unsigned), h->stream));
+    SBX_HIP(h, hipMemsetAsync(tile_tokens + tiles, 0, sizeof(unsigned), h->stream));
+    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_line_count, dim3(tiles), dim3(MX_THREADS), text, bytes, tile_lines);
+    SBX_KLAUNCH(h, SBX_K_MTX, k_mtx_count, dim3(tiles), dim3(MX_THREADS), text, bytes, tile_tokens);
+    SBX_LAUNCH_CHECK(h);
+    SBX_TRY(sbx_exclusive_scan_u32(h, tile_lines, tile_lines, (int64_t)tiles + 1, nullptr));
+    SBX_TRY(sbx_exclusive_scan_u32(h, tile_tokens, tile_tokens, (int64_t)tiles + 1, nullptr));
+    SBX_TRY(sbx_readback(h, &lines, tile_lines + tiles, sizeof(unsigned)));
+    SBX_TRY(sbx_readback(h, &tokens, tile_tokens + tiles, sizeof(unsigned)));
+  }
+  SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_off));
+  SBX_TRY(sbx_salloc(h, (size_t)tokens + 1, &tok_off));
+  if (lines) {
+    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_line_offsets, dim3(tiles), dim3(MX_THREADS), text, bytes, (const unsigned *)tile_lines,
+                (int64_t)lines, line_off);
+    if (tokens)
+      SBX_KLAUNCH(h, SBX_K_MTX, k_mtx_offsets, dim3(tiles), dim3(MX_THREADS), text, bytes, (const unsigned *)tile_tokens,
+                  (int64_t)tokens, tok_off);
+    SBX_LAUNCH_CHECK(h);
+  }
+  // (2) per line: first token, entries, comment; scans: first entry and vertex of every line
+  unsigned *line_tok = nullptr, *line_ent = nullptr, *line_ncb = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_tok));
+  SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_ent));
+  SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_ncb));
+  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_lines, dim3(gr_grid((int64_t)lines + 1)), dim3(MX_THREADS), text,
+              (const unsigned *)line_off, (int64_t)lines, (const unsigned *)tok_off, (int64_t)tokens, nvw,
+              edge_weighted ? 1 : 0, line_tok, line_ent, line_ncb, status);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(sbx_exclusive_scan_u32(h, line_ent, line_ent, (int64_t)lines + 1, nullptr));
+  SBX_TRY(sbx_exclusive_scan_u32(h, line_ncb, line_ncb, (int64_t)lines + 1, nullptr));
+  unsigned found = 0, vertex_lines = 0, st = 0;
+  SBX_TRY(sbx_readback(h, &found, line_ent + lines, sizeof(unsigned)));
+  SBX_TRY(sbx_readback(h, &vertex_lines, line_ncb + lines, sizeof(unsigned)));
+  SBX_TRY(sbx_readback(h, &st, status, sizeof(unsigned)));
+  if ((int64_t)vertex_lines > n)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_parse: the text has %u vertex lines, the header's n is %lld", vertex_lines,
+             (long long)n);
+  if (st & GR_ODD_LINE)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_parse: a line of an edge-weighted file has a neighbour without a weight");
+  if ((int64_t)found != nnz)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_parse: the lines hold %u neighbours, the header's m = %lld needs %lld", found,
+             (long long)m, (long long)nnz);
+  // (3) row offsets, then the tokens
+  int32_t *rp = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)n_dim + 1, &rp));
+  if (lines)
+    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_lines, dim3(gr_grid(lines)), dim3(MX_THREADS), (const unsigned *)line_ent,
+                (const unsigned *)line_ncb, (int64_t)lines, base, rp);
+  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_rest, dim3(gr_grid(n_dim + 1)), dim3(MX_THREADS), n_dim, base,
+              (int64_t)vertex_lines, (int32_t)nnz, rp);
+  SBX_LAUNCH_CHECK(h);
+  if (vwgt) SBX_HIP(h, hipMemsetAsync(vwgt, 0, (size_t)n_dim * (size_t)ncon * (size_t)vbytes, h->stream));
+  int32_t *r32 = (int32_t *)row_out, *c32 = (int32_t *)col_out;
+  if (wide_ids && nnz) {
+    SBX_TRY(sbx_salloc(h, (size_t)nnz, &r32));
+    SBX_TRY(sbx_salloc(h, (size_t)nnz, &c32));
+  }
+  if (tokens) {
+    const uint64_t *pow5 = nullptr;
+    const bool values = val || vwgt;
+    if (values) SBX_TRY(sbx_pow5_table(h, &pow5));
+    const int vkind = !values ? 0 : (vt == SBX_V_F32 ? 2 : vt == SBX_V_F64 ? 3 : 1);
+    const int vsigned = (vt == SBX_V_I32 || vt == SBX_V_I64) ? 1 : 0;
+#define TOKENS(VK, VBX)                                                                                                  \
+  SBX_KLAUNCH(h, SBX_K_MTX, (k_gr_tokens<VK, VBX>), dim3(gr_grid(tokens)), dim3(MX_THREADS), text, bytes,                  \
+              (const unsigned *)tok_off, (int64_t)tokens, (const unsigned *)line_off, (int64_t)lines,                      \
+              (const unsigned *)line_tok, (const unsigned *)line_ent, (const unsigned *)line_ncb, nvw, ncon,               \
+              edge_weighted ? 1 : 0, zero_index ? 1 : 0, n_dim, nnz, vsigned, pow5, r32, c32, val, vwgt, status)
+    if (vkind == 0) TOKENS(0, 4);
+    else if (vkind == 1 && vbytes == 4) TOKENS(1, 4);
+    else if (vkind == 1) TOKENS(1, 8);
+    else if (vkind == 2) TOKENS(2, 4);
+    else TOKENS(3, 8);
+#undef TOKENS
+    SBX_LAUNCH_CHECK(h);
+    SBX_PROF_BYTES(h, SBX_K_MTX, bytes + nnz * (int64_t)(8 + (val ? vbytes : 0)));
+    SBX_TRY(sbx_readback(h, &st, status, sizeof(unsigned)));
+    if (st & GR_TOO_MANY_DIGITS)
+      SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_parse: a value has more than 38 significant digits");
+    if (st & GR_ID_RANGE)
+      SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_parse: a neighbour id outside [%d, %lld]", zero_index ? 1 : 0,
+               (long long)(zero_index ? n_dim : n_dim - 1));
+    if (st)
+      SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_parse: malformed %s",
+               (st & GR_BAD_ID) && (st & GR_BAD_VALUE) ? "neighbour id and weight tokens"
+               : (st & GR_BAD_ID)                      ? "neighbour id token"
+                                                       : "weight token");
+  }
+  // (4) the inside of the rows, if one of them is out of order
+  if (nnz > 1) {
+    int sorted = 1;
+    SBX_TRY(sbx_csr_rows_sorted(h, SBX_I32, n_dim, rp, c32, &sorted));
+    if (!sorted) {
+      int32_t *ctmp = nullptr;
+      char *vtmp = nullptr;
+      const int vb = val ? vbytes : 0;
+      SBX_TRY(sbx_salloc(h, (size_t)nnz, &ctmp));
+      SBX_HIP(h, hipMemcpyAsync(ctmp, c32, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+      if (vb) {
+        SBX_TRY(sbx_salloc(h, (size_t)nnz * vb, &vtmp));
+        SBX_HIP(h, hipMemcpyAsync(vtmp, val, (size_t)nnz * vb, hipMemcpyDeviceToDevice, h->stream));
+      }
+      SBX_TRY(sbx_sort_segments(h, vb, n_dim, n_dim, nnz, rp, ctmp, vtmp, c32, val));  // stable: file order among equals
+    }
+  }
+  if (wide_ids && nnz) {
+    SBX_TRY(sbx_widen_i32(h, r32, row_out, nnz));
+    SBX_TRY(sbx_widen_i32(h, c32, col_out, nnz));
+  }
+  if (row_ptr_out) {
+    if (wide_offsets) SBX_TRY(sbx_widen_i32(h, rp, row_ptr_out, n_dim + 1));
+    else SBX_HIP(h, hipMemcpyAsync(row_ptr_out, rp, (size_t)(n_dim + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+  }
+  dims_nnz_host[0] = n_dim;
+  dims_nnz_host[1] = nnz;
+  return SBX_OK;
+}
+
+template <typename RP, typename CI>
+static int gr_format_typed(sbx_handle_t h, GrJob job, void *text_out, int64_t capacity, int64_t *bytes_host) {
+  // the ends of the range, and that the offsets between them ascend (the item search relies on it)
+  int64_t *ends = nullptr;
+  unsigned *descending = nullptr;
+  SBX_TRY(sbx_salloc(h, 2, &ends));
+  SBX_TRY(sbx_salloc(h, 1, &descending));
+  SBX_HIP(h, hipMemsetAsync(descending, 0, sizeof(unsigned), h->stream));
+  const int64_t rows = job.re - job.rb;
+  SBX_KLAUNCH(h, SBX_K_TEXT_CHECK, k_gr_range_ends<RP>, dim3(tx_grid(rows)), dim3(TX_THREADS), (const RP *)job.rp, job.rb,
+              job.re, ends, descending);
+  SBX_LAUNCH_CHECK(h);
+  int64_t hends[2] = {0, 0};
+  unsigned hdesc = 0;
+  SBX_TRY(sbx_readback(h, hends, ends, sizeof(hends)));
+  SBX_TRY(sbx_readback(h, &hdesc, descending, sizeof(unsigned)));
+  if (hdesc || hends[0] < 0) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: row_ptr descends inside the row range");
+  const int64_t entries = hends[1] - hends[0];
+  job.e0 = hends[0];
+  job.items = entries + rows * (int64_t)(1 + job.nvw) + 1;
+  if (job.items >= ((int64_t)1 << 32))
+    SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_format: 2^32 items and more in one call (pass the rows in sub-ranges)");
+  if (job.vkind == GV_RECORD) {
+    sbx_decrec *rec = nullptr;
+    if (job.ew && entries) {
+      SBX_TRY(tx_records(h, (const char *)job.val + hends[0] * job.vb, nullptr, entries, job.vb, job.precision, &rec));
+      job.rec_val = rec;
+    }
+    if (job.nvw) {
+      SBX_TRY(tx_records(h, (const char *)job.vwgt + job.rb * job.ncon * (int64_t)job.vb, nullptr, rows * job.ncon, job.vb,
+                         job.precision, &rec));
+      job.rec_vw = rec;
+    }
+  }
+  const unsigned grid = tx_grid(job.items);
+  int64_t *block_len = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &block_len));
+  SBX_HIP(h, hipMemsetAsync(block_len + grid, 0, sizeof(int64_t), h->stream));
+  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, (k_gr_lengths<RP, CI>), dim3(grid), dim3(TX_THREADS), job, block_len);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(sbx_exclusive_scan_i64(h, block_len, block_len, (int64_t)grid + 1, nullptr));
+  int64_t total = 0;
+  SBX_TRY(sbx_readback(h, &total, block_len + grid, sizeof(int64_t)));
+  *bytes_host = total;
+  if (!text_out) return SBX_OK;  // the sizing call
+  if (capacity < total)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: the text has %lld bytes, text_out holds %lld", (long long)total,
+             (long long)capacity);
+  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, (k_gr_write<RP, CI>), dim3(grid), dim3(TX_THREADS), job, (const int64_t *)block_len,
+              (char *)text_out);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, entries * (int64_t)(sizeof(CI) + job.vb) + total);
+  return SBX_OK;
+}
+
+extern "C" int sbgr_metis_format(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t row_begin, int64_t row_end,
+                                 const void *row_ptr, const void *col, const void *val, const void *vwgt, int ncon,
+                                 int64_t index_base, int precision, unsigned flags, void *text_out, int64_t capacity,
+                                 int64_t *bytes_host) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, bytes_host && capacity >= 0 && ncon >= 0, "bad argument");
+  SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64 || it == SBX_I32_N64, "unknown index type");
+  SBX_REQUIRE(h, row_begin >= 0 && row_end >= row_begin, "row range");
+  SBX_REQUIRE(h, precision >= 1 && precision <= 17, "precision: 1..17");
+  SBX_REQUIRE(h, (flags & ~(SBGR_EDGE_WEIGHTS | SBGR_VERTEX_WEIGHTS)) == 0, "unknown flag");
+  const int vbytes = sbx_value_bytes(vt);
+  SBX_REQUIRE(h, vbytes >= 0, "unknown value type");
+  const bool ew = (flags & SBGR_EDGE_WEIGHTS) != 0, vw = (flags & SBGR_VERTEX_WEIGHTS) != 0;
+  SBX_REQUIRE(h, !ew || (val && vt != SBX_V_NONE), "SBGR_EDGE_WEIGHTS needs values");
+  SBX_REQUIRE(h, !vw || vt != SBX_V_NONE, "SBGR_VERTEX_WEIGHTS needs a value type");
+  SBX_REQUIRE(h, !vw || ncon == 0 || vwgt, "SBGR_VERTEX_WEIGHTS with ncon > 0 needs vwgt");
+  *bytes_host = 0;
+  SBX_TRY(sbx_arena_begin(h));
+  if (row_end == row_begin) return SBX_OK;
+  SBX_REQUIRE(h, row_ptr, "row_ptr is needed");
+  NestGuard guard(h);
+  GrJob job = {};
+  job.rp = row_ptr;
+  job.col = col;
+  job.val = val;
+  job.vwgt = vwgt;
+  job.rb = row_begin;
+  job.re = row_end;
+  job.base = index_base;
+  job.ncon = ncon;
+  job.nvw = vw ? ncon : 0;
+  job.ew = ew ? 1 : 0;
+  job.vw = vw ? 1 : 0;
+  job.vb = vbytes;
+  job.precision = precision;
+  job.vkind = (vt == SBX_V_F32 || vt == SBX_V_F64) ? GV_RECORD
+              : (vt == SBX_V_I32 || vt == SBX_V_I64) ? GV_SIGNED
+              : vt == SBX_V_NONE ? GV_NONE : GV_UNSIGNED;
+  if (it == SBX_I64) return gr_format_typed<int64_t, int64_t>(h, job, text_out, capacity, bytes_host);
+  if (it == SBX_I32_N64) return gr_format_typed<int64_t, int32_t>(h, job, text_out, capacity, bytes_host);
+  return gr_format_typed<int32_t, int32_t>(h, job, text_out, capacity, bytes_host);
+}

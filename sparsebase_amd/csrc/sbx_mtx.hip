@@ -49,22 +49,10 @@ __global__ __launch_bounds__(MX_THREADS) void k_mtx_parse(const char *__restrict
   if (VKIND != 0) {
     const int64_t s = tok_off[l * fields + 2];
     const int64_t len = mx_token_len(text, bytes, s);
-    if (VKIND == 1) {
-      long long v = 0;
-      if (sbx_parse_integer(text + s, len, &v)) bad |= MX_BAD_VALUE;
-      if (VB == 4) {
-        if (value_signed ? (v < -2147483648ll || v > 2147483647ll) : (v < 0 || v > 4294967295ll)) bad |= MX_BAD_VALUE;
-      } else if (!value_signed && v < 0) {
-        bad |= MX_BAD_VALUE;
-      }
-      vbits = (uint64_t)v;
-    } else {
-      const sbx_decimal d = sbx_parse_decimal(text + s, len);
-      if (d.status == 1) bad |= MX_BAD_VALUE;
-      if (d.status == 2) bad |= MX_TOO_MANY_DIGITS;
-      if (VKIND == 2) vbits = (uint64_t)(sbx_decimal_to_float_bits(d, pow5) | ((uint32_t)d.neg << 31));
-      else vbits = sbx_decimal_to_double_bits(d, pow5) | ((uint64_t)d.neg << 63);
-    }
+    unsigned vf = 0;
+    vbits = mx_parse_value<VKIND, VB>(text + s, len, value_signed, pow5, &vf);
+    if (vf & MX_VALUE_BAD) bad |= MX_BAD_VALUE;
+    if (vf & MX_VALUE_DIGITS) bad |= MX_TOO_MANY_DIGITS;
   }
   if (upper && symmetry != 0) {  // :368-384: keep the entry in the upper triangle, no mirror
     const long long a = m < n ? m : n, b = m < n ? n : m;

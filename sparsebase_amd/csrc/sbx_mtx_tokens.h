@@ -1,7 +1,9 @@
 // sbx_mtx_tokens.h — the tokenizer of the text parsers: whitespace-separated tokens of a device text buffer, their
 // starts counted per tile and compacted in file order (count, scan, write).  Shared by the coordinate / edge-list
-// parsers (sbx_mtx.hip) and the array-format parser (sbx_dense.hip).
+// parsers (sbx_mtx.hip), the array-format parser (sbx_dense.hip) and the METIS graph parser (sbx_metis.hip), with the
+// conversion of a value token that the three share.
 #pragma once
+#include "sbx_dec2bin.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
 
@@ -74,6 +76,30 @@ __device__ __forceinline__ int64_t mx_token_len(const char *__restrict__ text, i
   int64_t e = start;
   while (e < bytes && !mx_space(text[e])) e++;
   return e - start;
+}
+
+// A value token -> the bits of a value of the type (VKIND 1 integer, 2 float, 3 double; VB its bytes): decimal integers
+// checked against the type's range, floating point by the exact decimal conversion of sbx_dec2bin.h.  *flags gets
+// MX_VALUE_BAD for a token the type cannot hold or that is no number, MX_VALUE_DIGITS for more than 38 significant digits.
+enum : unsigned { MX_VALUE_BAD = 1u, MX_VALUE_DIGITS = 2u };
+template <int VKIND, int VB>
+__device__ __forceinline__ uint64_t mx_parse_value(const char *__restrict__ s, int64_t len, int value_signed,
+                                                   const uint64_t *__restrict__ pow5, unsigned *flags) {
+  if (VKIND == 1) {
+    long long v = 0;
+    if (sbx_parse_integer(s, len, &v)) *flags |= MX_VALUE_BAD;
+    if (VB == 4) {
+      if (value_signed ? (v < -2147483648ll || v > 2147483647ll) : (v < 0 || v > 4294967295ll)) *flags |= MX_VALUE_BAD;
+    } else if (!value_signed && v < 0) {
+      *flags |= MX_VALUE_BAD;
+    }
+    return (uint64_t)v;
+  }
+  const sbx_decimal d = sbx_parse_decimal(s, len);
+  if (d.status == 1) *flags |= MX_VALUE_BAD;
+  if (d.status == 2) *flags |= MX_VALUE_DIGITS;
+  if (VKIND == 2) return (uint64_t)(sbx_decimal_to_float_bits(d, pow5) | ((uint32_t)d.neg << 31));
+  return sbx_decimal_to_double_bits(d, pow5) | ((uint64_t)d.neg << 63);
 }
 
 // an entry point that calls other entry points: the arena is not rewound while one of these lives

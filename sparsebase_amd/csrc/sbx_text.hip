@@ -22,13 +22,9 @@
 #include "sbx_device.h"
 #include "sbx_internal.h"
 #include "sbx_text.h"
+#include "sbx_text_emit.h"  // integer printing, decimal records, the LDS write-out: shared with sbx_metis.hip
 
 namespace {
-
-constexpr int TX_THREADS = 256;
-constexpr int TX_LINE_MAX = 68;  // 2 x 20 index characters, 2 blanks, SBX_DEC_MAX_CHARS, '\n', rounded up
-constexpr int TX_LDS = TX_THREADS * TX_LINE_MAX + 16;
-static_assert(20 + 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 1 <= TX_LINE_MAX, "a line fits its LDS slot");
 
 enum : int { TV_NONE = 0, TV_SIGNED, TV_UNSIGNED, TV_RECORD, TV_ZERO };
 
@@ -49,17 +45,6 @@ __device__ __forceinline__ bool tx_keep(unsigned flags, int64_t r, int64_t c) {
   if ((flags & SBX_TEXT_NO_DIAGONAL) && c == r) return false;
   return true;
 }
-__device__ __forceinline__ int tx_len_signed(int64_t v) {
-  return v < 0 ? 1 + sbx_b2d::length_u64(0ull - (uint64_t)v) : sbx_b2d::length_u64((uint64_t)v);
-}
-__device__ __forceinline__ int tx_emit_signed(int64_t v, char *dst) {
-  if (v < 0) {
-    dst[0] = '-';
-    return 1 + sbx_b2d::emit_u64(0ull - (uint64_t)v, dst + 1);
-  }
-  return sbx_b2d::emit_u64((uint64_t)v, dst);
-}
-
 // the integer value of line i: false where the dense cell holds nothing
 __device__ __forceinline__ bool tx_source(const TextJob &j, int64_t i, int64_t *src) {
   *src = i;
@@ -118,54 +103,6 @@ __device__ __forceinline__ void tx_line_emit(const TextJob &j, int64_t i, char *
   dst[o] = '\n';
 }
 
-// ---- 1 / 2: values -> decimal records
-template <int BITS>
-__device__ __forceinline__ uint64_t tx_bits(const void *val, const int32_t *slot, int64_t i, bool *stored) {
-  int64_t src = i;
-  *stored = true;
-  if (slot) {
-    const int32_t s = slot[i];
-    if (s < 0) {
-      *stored = false;
-      return 0;
-    }
-    src = s;
-  }
-  return BITS == 64 ? ((const uint64_t *)val)[src] : (uint64_t)((const uint32_t *)val)[src];
-}
-
-template <int BITS>
-__global__ __launch_bounds__(TX_THREADS) void k_text_records(const void *__restrict__ val, const int32_t *__restrict__ slot,
-                                                             int64_t count, int precision,
-                                                             const uint64_t *__restrict__ pow5, sbx_decrec *__restrict__ rec,
-                                                             unsigned *__restrict__ long_list, unsigned *__restrict__ long_count) {
-  const int64_t i = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  bool lng = false;
-  if (i < count) {
-    bool stored;
-    const uint64_t bits = tx_bits<BITS>(val, slot, i, &stored);  // (an empty cell: +0, which prints as "0")
-    const sbx_decrec r = sbx_b2d::to_record<false, BITS>(bits, precision, pow5);
-    lng = (r.kind >> 1) == SBX_DEC_LONG;
-    rec[i] = r;
-  }
-  const unsigned pos = sbx_wave_append(long_count, lng);  // (every lane calls it)
-  if (lng) long_list[pos] = (unsigned)i;
-}
-
-template <int BITS>
-__global__ __launch_bounds__(TX_THREADS) void k_text_long(const void *__restrict__ val, const int32_t *__restrict__ slot,
-                                                          int precision, const uint64_t *__restrict__ pow5,
-                                                          sbx_decrec *__restrict__ rec, const unsigned *__restrict__ long_list,
-                                                          const unsigned *__restrict__ long_count) {
-  const unsigned total = *long_count;
-  for (unsigned k = blockIdx.x * TX_THREADS + threadIdx.x; k < total; k += gridDim.x * TX_THREADS) {
-    const int64_t i = long_list[k];
-    bool stored;
-    const uint64_t bits = tx_bits<BITS>(val, slot, i, &stored);
-    rec[i] = sbx_b2d::to_record<true, BITS>(bits, precision, pow5);
-  }
-}
-
 // ---- 3 / 4: lengths, write-out
 __global__ __launch_bounds__(TX_THREADS) void k_text_lengths(const TextJob j, int64_t *__restrict__ block_len) {
   __shared__ unsigned s_red[TX_THREADS / 64 + 1];
@@ -186,15 +123,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_text_write(const TextJob j, cons
   const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
   if (len) tx_line_emit(j, i, s_text + phase + off);
   __syncthreads();
-  unsigned head = (16u - phase) & 15u;
-  if (head > total) head = total;
-  const unsigned words = (total - head) >> 4, tail = (total - head) & 15u;
-  if (threadIdx.x < head) dst[threadIdx.x] = s_text[phase + threadIdx.x];
-  const uint4 *src16 = (const uint4 *)(s_text + phase + head);
-  uint4 *dst16 = (uint4 *)(dst + head);
-  for (unsigned w = threadIdx.x; w < words; w += TX_THREADS) dst16[w] = src16[w];
-  const unsigned t0 = head + (words << 4);
-  if (threadIdx.x < tail) dst[t0 + threadIdx.x] = s_text[phase + t0 + threadIdx.x];
+  tx_block_store(s_text, phase, total, dst);
 }
 
 // ---- symmetry check
@@ -373,8 +302,6 @@ static int tx_value_kind(sbx_value_type vt) {
   return -1;
 }
 
-static unsigned tx_grid(int64_t count) { return (unsigned)((count + TX_THREADS - 1) / TX_THREADS); }
-
 // steps 1 to 4 for a job whose arrays are set; the caller has begun the arena and holds a NestGuard
 static int tx_format(sbx_handle_t h, const char *who, TextJob job, void *text_out, int64_t capacity, int64_t *bytes_host) {
   *bytes_host = 0;
@@ -384,28 +311,8 @@ static int tx_format(sbx_handle_t h, const char *who, TextJob job, void *text_ou
     SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: 2^32 lines and more in one call (pass the entries in sub-ranges)", who);
   const unsigned grid = tx_grid(count);
   if (job.vkind == TV_RECORD) {
-    const uint64_t *pow5 = nullptr;
-    SBX_TRY(sbx_pow5_table(h, &pow5));
     sbx_decrec *rec = nullptr;
-    unsigned *long_list = nullptr, *long_count = nullptr;
-    SBX_TRY(sbx_salloc(h, (size_t)count, &rec));
-    SBX_TRY(sbx_salloc(h, (size_t)count, &long_list));
-    SBX_TRY(sbx_salloc(h, 1, &long_count));
-    SBX_HIP(h, hipMemsetAsync(long_count, 0, sizeof(unsigned), h->stream));
-    const unsigned lgrid = grid < 1024u ? grid : 1024u;
-    if (job.vb == 8) {
-      SBX_KLAUNCH(h, SBX_K_TEXT_FORMAT, k_text_records<64>, dim3(grid), dim3(TX_THREADS), job.val, job.slot, count,
-                  job.precision, pow5, rec, long_list, long_count);
-      SBX_KLAUNCH(h, SBX_K_TEXT_LONG, k_text_long<64>, dim3(lgrid), dim3(TX_THREADS), job.val, job.slot, job.precision, pow5,
-                  rec, (const unsigned *)long_list, (const unsigned *)long_count);
-    } else {
-      SBX_KLAUNCH(h, SBX_K_TEXT_FORMAT, k_text_records<32>, dim3(grid), dim3(TX_THREADS), job.val, job.slot, count,
-                  job.precision, pow5, rec, long_list, long_count);
-      SBX_KLAUNCH(h, SBX_K_TEXT_LONG, k_text_long<32>, dim3(lgrid), dim3(TX_THREADS), job.val, job.slot, job.precision, pow5,
-                  rec, (const unsigned *)long_list, (const unsigned *)long_count);
-    }
-    SBX_LAUNCH_CHECK(h);
-    SBX_PROF_BYTES(h, SBX_K_TEXT_FORMAT, count * (int64_t)(job.vb + sizeof(sbx_decrec)));
+    SBX_TRY(tx_records(h, job.val, job.slot, count, job.vb, job.precision, &rec));
     job.rec = rec;
   }
   const int64_t line_in = (job.coords ? 2 * (job.idx64 ? 8 : 4) : 0) + (job.slot ? 4 : 0) +

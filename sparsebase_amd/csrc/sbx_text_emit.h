@@ -1,0 +1,123 @@
+// sbx_text_emit.h — what the text formatters share: integer printing, floating-point values -> decimal records
+// (sbx_bin2dec.h) and the write-out of a workgroup's LDS text image in aligned 16-byte words.  Used by the Matrix Market /
+// edge-list formatters (sbx_text.hip) and the METIS graph formatter (sbx_metis.hip).
+#pragma once
+#include "sbx_bin2dec.h"
+#include "sbx_device.h"
+#include "sbx_internal.h"
+
+namespace {  // (kernels in a header shared by several translation units: internal linkage)
+
+constexpr int TX_THREADS = 256;
+constexpr int TX_LINE_MAX = 68;  // 2 x 20 index characters, 2 blanks, SBX_DEC_MAX_CHARS, '\n', rounded up
+constexpr int TX_LDS = TX_THREADS * TX_LINE_MAX + 16;
+static_assert(20 + 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 1 <= TX_LINE_MAX, "a line fits its LDS slot");
+
+__device__ __forceinline__ int tx_len_signed(int64_t v) {
+  return v < 0 ? 1 + sbx_b2d::length_u64(0ull - (uint64_t)v) : sbx_b2d::length_u64((uint64_t)v);
+}
+__device__ __forceinline__ int tx_emit_signed(int64_t v, char *dst) {
+  if (v < 0) {
+    dst[0] = '-';
+    return 1 + sbx_b2d::emit_u64(0ull - (uint64_t)v, dst + 1);
+  }
+  return sbx_b2d::emit_u64((uint64_t)v, dst);
+}
+
+// ---- values -> decimal records
+template <int BITS>
+__device__ __forceinline__ uint64_t tx_bits(const void *val, const int32_t *slot, int64_t i, bool *stored) {
+  int64_t src = i;
+  *stored = true;
+  if (slot) {
+    const int32_t s = slot[i];
+    if (s < 0) {
+      *stored = false;
+      return 0;
+    }
+    src = s;
+  }
+  return BITS == 64 ? ((const uint64_t *)val)[src] : (uint64_t)((const uint32_t *)val)[src];
+}
+
+template <int BITS>
+__global__ __launch_bounds__(TX_THREADS) void k_text_records(const void *__restrict__ val, const int32_t *__restrict__ slot,
+                                                             int64_t count, int precision,
+                                                             const uint64_t *__restrict__ pow5, sbx_decrec *__restrict__ rec,
+                                                             unsigned *__restrict__ long_list, unsigned *__restrict__ long_count) {
+  const int64_t i = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  bool lng = false;
+  if (i < count) {
+    bool stored;
+    const uint64_t bits = tx_bits<BITS>(val, slot, i, &stored);  // (an empty cell: +0, which prints as "0")
+    const sbx_decrec r = sbx_b2d::to_record<false, BITS>(bits, precision, pow5);
+    lng = (r.kind >> 1) == SBX_DEC_LONG;
+    rec[i] = r;
+  }
+  const unsigned pos = sbx_wave_append(long_count, lng);  // (every lane calls it)
+  if (lng) long_list[pos] = (unsigned)i;
+}
+
+template <int BITS>
+__global__ __launch_bounds__(TX_THREADS) void k_text_long(const void *__restrict__ val, const int32_t *__restrict__ slot,
+                                                          int precision, const uint64_t *__restrict__ pow5,
+                                                          sbx_decrec *__restrict__ rec, const unsigned *__restrict__ long_list,
+                                                          const unsigned *__restrict__ long_count) {
+  const unsigned total = *long_count;
+  for (unsigned k = blockIdx.x * TX_THREADS + threadIdx.x; k < total; k += gridDim.x * TX_THREADS) {
+    const int64_t i = long_list[k];
+    bool stored;
+    const uint64_t bits = tx_bits<BITS>(val, slot, i, &stored);
+    rec[i] = sbx_b2d::to_record<true, BITS>(bits, precision, pow5);
+  }
+}
+
+// The workgroup's `total` bytes of text, which lie in s_text from byte `phase` = dst & 15 on (so that LDS words and global
+// words coincide), go to dst in aligned 16-byte words, with at most 15 single bytes at either end.  Every thread of the
+// workgroup calls it behind the barrier that ends the writes to s_text; nothing at or beyond dst + total is touched.
+__device__ __forceinline__ void tx_block_store(const char *s_text, unsigned phase, unsigned total, char *dst) {
+  unsigned head = (16u - phase) & 15u;
+  if (head > total) head = total;
+  const unsigned words = (total - head) >> 4, tail = (total - head) & 15u;
+  if (threadIdx.x < head) dst[threadIdx.x] = s_text[phase + threadIdx.x];
+  const uint4 *src16 = (const uint4 *)(s_text + phase + head);
+  uint4 *dst16 = (uint4 *)(dst + head);
+  for (unsigned w = threadIdx.x; w < words; w += TX_THREADS) dst16[w] = src16[w];
+  const unsigned t0 = head + (words << 4);
+  if (threadIdx.x < tail) dst[t0 + threadIdx.x] = s_text[phase + t0 + threadIdx.x];
+}
+
+static unsigned tx_grid(int64_t count) { return (unsigned)((count + TX_THREADS - 1) / TX_THREADS); }
+
+// the decimal records of `count` floating-point values of vb bytes (steps 1 and 2 of a formatter): the 128-bit fast path,
+// then the listed values through the multi-limb path; the caller has begun the arena
+static int tx_records(sbx_handle_t h, const void *val, const int32_t *slot, int64_t count, int vb, int precision,
+                      sbx_decrec **rec_out) {
+  const uint64_t *pow5 = nullptr;
+  SBX_TRY(sbx_pow5_table(h, &pow5));
+  sbx_decrec *rec = nullptr;
+  unsigned *long_list = nullptr, *long_count = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)count, &rec));
+  SBX_TRY(sbx_salloc(h, (size_t)count, &long_list));
+  SBX_TRY(sbx_salloc(h, 1, &long_count));
+  SBX_HIP(h, hipMemsetAsync(long_count, 0, sizeof(unsigned), h->stream));
+  const unsigned grid = tx_grid(count);
+  const unsigned lgrid = grid < 1024u ? grid : 1024u;
+  if (vb == 8) {
+    SBX_KLAUNCH(h, SBX_K_TEXT_FORMAT, k_text_records<64>, dim3(grid), dim3(TX_THREADS), val, slot, count, precision, pow5,
+                rec, long_list, long_count);
+    SBX_KLAUNCH(h, SBX_K_TEXT_LONG, k_text_long<64>, dim3(lgrid), dim3(TX_THREADS), val, slot, precision, pow5, rec,
+                (const unsigned *)long_list, (const unsigned *)long_count);
+  } else {
+    SBX_KLAUNCH(h, SBX_K_TEXT_FORMAT, k_text_records<32>, dim3(grid), dim3(TX_THREADS), val, slot, count, precision, pow5,
+                rec, long_list, long_count);
+    SBX_KLAUNCH(h, SBX_K_TEXT_LONG, k_text_long<32>, dim3(lgrid), dim3(TX_THREADS), val, slot, precision, pow5, rec,
+                (const unsigned *)long_list, (const unsigned *)long_count);
+  }
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_TEXT_FORMAT, count * (int64_t)(vb + sizeof(sbx_decrec)));
+  *rec_out = rec;
+  return SBX_OK;
+}
+
+}  // namespace

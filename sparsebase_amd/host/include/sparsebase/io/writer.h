@@ -43,17 +43,19 @@ class TextStreamer {
   template <typename F>
   void Stream(std::ostream &out, int64_t entries, F call) {
     const int64_t chunk = (int64_t)(SBX_TEXT_CHUNK_ENTRIES);
-    for (int64_t b = 0; b < entries; b += chunk) {
-      const int64_t count = std::min<int64_t>(chunk, entries - b);
-      int64_t bytes = 0;
-      int rc = call(b, count, (void *)d_text_, cap_, &bytes);
-      if ((d_text_ == nullptr || rc == SBX_ERR_BAD_ARG) && bytes > cap_) {
-        Reserve(bytes + bytes / 8);
-        rc = call(b, count, (void *)d_text_, cap_, &bytes);
-      }
-      WriterCheck(dev_, rc);
-      Flush(out, bytes);
+    for (int64_t b = 0; b < entries; b += chunk) Chunk(out, b, std::min<int64_t>(chunk, entries - b), call);
+  }
+  // one chunk of a caller that cuts its chunks itself (the METIS graph writer: rows of unequal length)
+  template <typename F>
+  void Chunk(std::ostream &out, int64_t begin, int64_t count, F call) {
+    int64_t bytes = 0;
+    int rc = call(begin, count, (void *)d_text_, cap_, &bytes);
+    if ((d_text_ == nullptr || rc == SBX_ERR_BAD_ARG) && bytes > cap_) {
+      Reserve(bytes + bytes / 8);
+      rc = call(begin, count, (void *)d_text_, cap_, &bytes);
     }
+    WriterCheck(dev_, rc);
+    Flush(out, bytes);
   }
   // a text that one call produces whole (the array format): formatted first, so that a refusal comes before any file
   template <typename F>

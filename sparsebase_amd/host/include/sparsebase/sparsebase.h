@@ -35,6 +35,9 @@
 #include "sparsebase/utils/logger.h"
 // last: the reader needs the complete conversion graph
 #include "sparsebase/bases/iobase.h"
+#include "sparsebase/io/metis_graph_reader.h"
+#include "sparsebase/io/metis_graph_writer.h"
+#include "sparsebase/object/object.h"
 
 namespace sparsebase {
 // pre-0.3 spelling used by north_star / older call sites (SURVEY.md "Naming drift")

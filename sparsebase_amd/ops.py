@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -739,3 +739,49 @@ def coo_undirected_unique_(row, col, val=None):
 
 
 coo_undirected_unique = coo_undirected_unique_
+
+
+# ----------------------------------------------------------------------------- METIS graph files (include/sbgr.h)
+def metis_parse(text, n, m, fmt=0, ncon=0, zero_index=True, index_dtype=torch.int32, value_dtype=None,
+                offset_dtype=None, row_ptr=True):
+    """text: uint8 device tensor with the bytes after the header line; n, m, fmt, ncon as sparsebase_amd.metis.parse_header
+    gives them.  Returns (n_dim, row, col, val, vwgt, row_ptr): the COO sorted by (row, col), the edge weights (None unless
+    the file has them and value_dtype is given), the n_dim x ncon vertex weights (None likewise) and the row offsets
+    (sbgr_metis_parse).  offset_dtype=torch.int64 over int32 ids is the <32-bit ids, 64-bit offsets> tuple."""
+    dev = _check_dev(text)
+    hd = handle_for(dev)
+    offset_dtype = index_dtype if offset_dtype is None else offset_dtype
+    it = _it(torch.empty(0, dtype=offset_dtype), torch.empty(0, dtype=index_dtype))
+    n_dim, nnz = n + (0 if zero_index else 1), 2 * m
+    edge_weighted, vertex_weighted = fmt in (1, 11), fmt >= 10 and ncon > 0
+    row = torch.empty(max(1, nnz), dtype=index_dtype, device=dev)
+    col = torch.empty(max(1, nnz), dtype=index_dtype, device=dev)
+    val = torch.empty(max(1, nnz), dtype=value_dtype, device=dev) if (edge_weighted and value_dtype is not None) else None
+    vwgt = torch.empty((max(0, n_dim), ncon), dtype=value_dtype, device=dev) \
+        if (vertex_weighted and value_dtype is not None) else None
+    rp = torch.empty(max(0, n_dim) + 1, dtype=offset_dtype, device=dev) if row_ptr else None
+    vt = capi.V_NONE if value_dtype is None else _VT[value_dtype]
+    dims = (C.c_int64 * 2)()
+    hd.check(hd.lib.sbgr_metis_parse(hd.h, it, vt, _p(text), text.numel(), n, m, fmt, ncon,
+                                     capi.GR_ZERO_INDEX if zero_index else 0, max(1, nnz), _p(row), _p(col), _p(val),
+                                     _p(vwgt), _p(rp), dims))
+    k = dims[1]
+    return dims[0], row[:k], col[:k], (None if val is None else val[:k]), vwgt, rp
+
+
+def metis_format(row_ptr, col, val=None, vwgt=None, row_begin=0, row_end=None, index_base=1, precision=6,
+                 edge_weights=False, vertex_weights=False, unsigned=False):
+    """The vertex lines of rows [row_begin, row_end) of a device CSR as MetisGraphWriter::WriteGraph writes them, a uint8
+    device tensor (sbgr_metis_format).  vwgt: rows x ncon values of val's dtype."""
+    dev = _check_dev(row_ptr, col, val, vwgt)
+    hd = handle_for(dev)
+    row_end = row_ptr.numel() - 1 if row_end is None else row_end
+    weights = val if val is not None else vwgt
+    if val is not None and vwgt is not None and val.dtype != vwgt.dtype:
+        raise TypeError("edge and vertex weights share one value type")
+    vt = capi.V_NONE if weights is None else _text_vt(weights, unsigned)
+    ncon = 0 if vwgt is None else (vwgt.shape[1] if vwgt.dim() == 2 else 1)
+    flags = (capi.GR_EDGE_WEIGHTS if edge_weights else 0) | (capi.GR_VERTEX_WEIGHTS if vertex_weights else 0)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbgr_metis_format(
+        hd.h, _it(row_ptr, col), vt, row_begin, row_end, _p(row_ptr), _p(col), _p(val), _p(vwgt), ncon, index_base,
+        precision, flags, out, cap, C.byref(nb)))
