@@ -32,6 +32,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbx_stats.h"))
     hs.append(os.path.join(ROOT, "include", "sbio.h"))
     hs.append(os.path.join(ROOT, "include", "sbgr.h"))
+    hs.append(os.path.join(ROOT, "include", "sbhg.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

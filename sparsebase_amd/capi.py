@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h and include/sbgr.h
+"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h and
+include/sbhg.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -21,6 +22,7 @@ SB_GREEDY, SB_HUB_ORDER = 1, 2
 TEXT_LOWER, TEXT_NO_DIAGONAL, TEXT_PATTERN = 1, 2, 4
 STAT_MEDIAN, STAT_LOG = 1, 2
 GR_ZERO_INDEX, GR_EDGE_WEIGHTS, GR_VERTEX_WEIGHTS = 1, 2, 4
+HG_NET_WEIGHTS, HG_NO_LAST_NEWLINE = 1, 2
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -161,6 +163,16 @@ GRAPH_PROTOTYPES = {
                            C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbhg.h declares (tests/test_hypergraph_abi.py checks header <-> library <-> this table): the PaToH
+# hypergraph format, prefix `sbhg_`
+HYPERGRAPH_PROTOTYPES = {
+    "sbhg_patoh_parse": ([_H, _int, _int, _vp, _i64, _i64, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                          C.POINTER(_i64)], _int),
+    "sbhg_cells_to_nets": ([_H, _int, _i64, _i64, _vp, _vp, _int, _vp, _vp], _int),
+    "sbhg_patoh_format": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _i64, _int, _u, _vp, _i64, C.POINTER(_i64)], _int),
+    "sbhg_patoh_format_weights": ([_H, _int, _i64, _i64, _vp, _int, _vp, _i64, C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -174,7 +186,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
-                                           list(GRAPH_PROTOTYPES.items())):
+                                           list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

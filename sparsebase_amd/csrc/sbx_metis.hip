@@ -24,70 +24,11 @@
 #include "sbx_internal.h"
 #include "sbx_mtx_tokens.h"
 #include "sbx_text_emit.h"
+#include "sbx_text_lines.h"
 
 namespace {
 
 enum : unsigned { GR_BAD_ID = 1u, GR_BAD_VALUE = 2u, GR_TOO_MANY_DIGITS = 4u, GR_ID_RANGE = 8u, GR_ODD_LINE = 16u };
-
-// ---- line starts: byte 0 and every byte behind a '\n' (a '\n' that ends the text starts nothing)
-__device__ __forceinline__ unsigned gr_line_starts(const char *__restrict__ text, int64_t bytes, int64_t p0) {
-  static_assert(MX_BPT == 16, "one 16-byte load per thread");
-  unsigned mask = 0;
-  bool prev_nl = p0 == 0 || text[p0 - 1] == '\n';
-  if (p0 + MX_BPT <= bytes && (((uintptr_t)text + (uintptr_t)p0) & 15) == 0) {
-    const uint4 v = *(const uint4 *)(text + p0);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < MX_BPT; k++) {
-      if (prev_nl) mask |= 1u << k;
-      prev_nl = (char)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) == '\n';
-    }
-    return mask;
-  }
-#pragma unroll
-  for (int k = 0; k < MX_BPT; k++) {
-    if (p0 + k >= bytes) break;
-    if (prev_nl) mask |= 1u << k;
-    prev_nl = text[p0 + k] == '\n';
-  }
-  return mask;
-}
-
-__global__ __launch_bounds__(MX_THREADS) void k_gr_line_count(const char *__restrict__ text, int64_t bytes,
-                                                              unsigned *__restrict__ tile_lines) {
-  __shared__ unsigned s_red[MX_THREADS / 64 + 1];
-  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
-  const unsigned c = p0 < bytes ? (unsigned)__popc(gr_line_starts(text, bytes, p0)) : 0u;
-  const unsigned tot = sbx_block_sum<unsigned, MX_THREADS>(c, s_red);
-  if (threadIdx.x == 0) tile_lines[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(MX_THREADS) void k_gr_line_offsets(const char *__restrict__ text, int64_t bytes,
-                                                                const unsigned *__restrict__ tile_base, int64_t lines,
-                                                                unsigned *__restrict__ line_off) {
-  __shared__ unsigned s_scan[MX_THREADS / 64 + 1];
-  const int64_t p0 = (int64_t)blockIdx.x * MX_TILE + (int64_t)threadIdx.x * MX_BPT;
-  unsigned mask = p0 < bytes ? gr_line_starts(text, bytes, p0) : 0u;
-  unsigned all;
-  unsigned t = tile_base[blockIdx.x] + sbx_block_exclusive_sum<unsigned, MX_THREADS>((unsigned)__popc(mask), s_scan, &all);
-  while (mask) {
-    const int k = __ffs(mask) - 1;
-    mask &= mask - 1;
-    if ((int64_t)t < lines) line_off[t] = (unsigned)(p0 + k);
-    t++;
-  }
-}
-
-// first index i in [0, len) with arr[i] >= target, or len
-__device__ __forceinline__ int64_t gr_lower_bound(const unsigned *__restrict__ arr, int64_t len, unsigned target) {
-  int64_t lo = 0, hi = len;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (arr[mid] < target) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // one thread per line, and one for the end of the arrays: first token, entries, comment or not
 __global__ __launch_bounds__(MX_THREADS) void k_gr_lines(const char *__restrict__ text, const unsigned *__restrict__ line_off,
@@ -104,8 +45,8 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_lines(const char *__restrict_
     return;
   }
   const unsigned start = line_off[l];
-  const int64_t a = gr_lower_bound(tok_off, tokens, start);
-  const int64_t b = l + 1 < lines ? gr_lower_bound(tok_off, tokens, line_off[l + 1]) : tokens;
+  const int64_t a = tl_lower_bound(tok_off, tokens, start);
+  const int64_t b = l + 1 < lines ? tl_lower_bound(tok_off, tokens, line_off[l + 1]) : tokens;
   const bool comment = text[start] == '%';
   int64_t k = b - a - nvw;  // neighbour (and edge weight) tokens
   if (k < 0) k = 0;
@@ -132,12 +73,6 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_row_ptr_rest(int64_t n_dim, i
   else if (r >= vertex_lines + base) rp[r] = nnz;
 }
 
-template <int VB>
-__device__ __forceinline__ void gr_store_value(char *__restrict__ dst, int64_t i, uint64_t bits) {
-  if (VB == 4) ((uint32_t *)dst)[i] = (uint32_t)bits;
-  else ((uint64_t *)dst)[i] = bits;
-}
-
 // one thread per token
 template <int VKIND /*0 none, 1 integer, 2 float, 3 double*/, int VB>
 __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict__ text, int64_t bytes,
@@ -154,7 +89,7 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= tokens) return;
   const unsigned s = tok_off[t];
-  const int64_t l = gr_lower_bound(line_off, lines, s + 1u) - 1;  // the last line that starts at or before the token
+  const int64_t l = tl_lower_bound(line_off, lines, s + 1u) - 1;  // the last line that starts at or before the token
   if (l < 0 || line_ncb[l + 1] == line_ncb[l]) return;            // (a token of a comment line does not exist)
   const int64_t vertex = (int64_t)line_ncb[l] + (zero_index ? 0 : 1);
   const int64_t ord = t - (int64_t)line_tok[l];
@@ -166,7 +101,7 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict
       const uint64_t bits = mx_parse_value<VKIND == 0 ? 1 : VKIND, VB>(text + s, len, value_signed, pow5, &vf);
       if (vf & MX_VALUE_BAD) bad |= GR_BAD_VALUE;
       if (vf & MX_VALUE_DIGITS) bad |= GR_TOO_MANY_DIGITS;
-      gr_store_value<VB>(vwgt, vertex * ncon + ord, bits);
+      tl_store_value<VB>(vwgt, vertex * ncon + ord, bits);
     }
   } else {
     const int64_t k = ord - nvw;
@@ -178,7 +113,7 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict
           const uint64_t bits = mx_parse_value<VKIND == 0 ? 1 : VKIND, VB>(text + s, len, value_signed, pow5, &vf);
           if (vf & MX_VALUE_BAD) bad |= GR_BAD_VALUE;
           if (vf & MX_VALUE_DIGITS) bad |= GR_TOO_MANY_DIGITS;
-          gr_store_value<VB>(val, pos, bits);
+          tl_store_value<VB>(val, pos, bits);
         }
       } else {
         long long id = 0;
@@ -201,7 +136,7 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict
 }
 
 // ---- the formatter
-enum : int { GV_NONE = 0, GV_SIGNED, GV_UNSIGNED, GV_RECORD };
+enum : int { GV_NONE = TI_NONE, GV_SIGNED = TI_SIGNED, GV_UNSIGNED = TI_UNSIGNED, GV_RECORD = TI_RECORD };
 
 struct GrJob {
   const void *rp, *col, *val, *vwgt;
@@ -231,15 +166,11 @@ __device__ __forceinline__ void gr_locate(const GrJob &j, int64_t k, int64_t *ro
 }
 
 __device__ __forceinline__ int gr_value_length(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel) {
-  if (j.vkind == GV_RECORD) return sbx_b2d::text_length(rec[irel], j.precision);
-  if (j.vkind == GV_SIGNED) return tx_len_signed(j.vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i]);
-  return sbx_b2d::length_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i]);
+  return tx_item_value_length(j.vkind, j.vb, j.precision, arr, rec, i, irel);
 }
 __device__ __forceinline__ int gr_value_emit(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel,
                                              char *dst) {
-  if (j.vkind == GV_RECORD) return sbx_b2d::emit(rec[irel], j.precision, dst);
-  if (j.vkind == GV_SIGNED) return tx_emit_signed(j.vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i], dst);
-  return sbx_b2d::emit_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i], dst);
+  return tx_item_value_emit(j.vkind, j.vb, j.precision, arr, rec, i, irel, dst);
 }
 
 // the text of item (r, sub): its length; written at dst unless dst is null
@@ -324,18 +255,6 @@ __global__ __launch_bounds__(TX_THREADS) void k_gr_write(const GrJob j, const in
   tx_block_store(s_text, phase, total, dst);
 }
 
-template <typename T>
-__global__ __launch_bounds__(TX_THREADS) void k_gr_range_ends(const T *__restrict__ rp, int64_t rb, int64_t re,
-                                                              int64_t *__restrict__ ends, unsigned *__restrict__ descending) {
-  // the offsets of the range's ends; whether the offsets of the range descend somewhere
-  const int64_t r = rb + (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  if (r == rb) {
-    ends[0] = (int64_t)rp[rb];
-    ends[1] = (int64_t)rp[re];
-  }
-  if (r < re && rp[r + 1] < rp[r]) atomicOr(descending, 1u);
-}
-
 }  // namespace
 
 #define SBX_REQUIRE(h, cond, msg)                                       \
@@ -376,36 +295,13 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
   SBX_TRY(sbx_arena_begin(h));
   NestGuard guard(h);
   const char *text = (const char *)text_dev;
-  const unsigned tiles = (unsigned)((bytes + MX_TILE - 1) / MX_TILE);
   unsigned *status = nullptr;
   SBX_TRY(sbx_salloc(h, 1, &status));
   SBX_HIP(h, hipMemsetAsync(status, 0, sizeof(unsigned), h->stream));
   // (1) line starts and token starts
   unsigned lines = 0, tokens = 0;
-  unsigned *tile_lines = nullptr, *tile_tokens = nullptr, *line_off = nullptr, *tok_off = nullptr;
-  if (tiles) {
-    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_lines));
-    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_tokens));
-    SBX_HIP(h, hipMemsetAsync(tile_lines + tiles, 0, sizeof(unsigned), h->stream));
-    SBX_HIP(h, hipMemsetAsync(tile_tokens + tiles, 0, sizeof(unsigned), h->stream));
-    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_line_count, dim3(tiles), dim3(MX_THREADS), text, bytes, tile_lines);
-    SBX_KLAUNCH(h, SBX_K_MTX, k_mtx_count, dim3(tiles), dim3(MX_THREADS), text, bytes, tile_tokens);
-    SBX_LAUNCH_CHECK(h);
-    SBX_TRY(sbx_exclusive_scan_u32(h, tile_lines, tile_lines, (int64_t)tiles + 1, nullptr));
-    SBX_TRY(sbx_exclusive_scan_u32(h, tile_tokens, tile_tokens, (int64_t)tiles + 1, nullptr));
-    SBX_TRY(sbx_readback(h, &lines, tile_lines + tiles, sizeof(unsigned)));
-    SBX_TRY(sbx_readback(h, &tokens, tile_tokens + tiles, sizeof(unsigned)));
-  }
-  SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_off));
-  SBX_TRY(sbx_salloc(h, (size_t)tokens + 1, &tok_off));
-  if (lines) {
-    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_line_offsets, dim3(tiles), dim3(MX_THREADS), text, bytes, (const unsigned *)tile_lines,
-                (int64_t)lines, line_off);
-    if (tokens)
-      SBX_KLAUNCH(h, SBX_K_MTX, k_mtx_offsets, dim3(tiles), dim3(MX_THREADS), text, bytes, (const unsigned *)tile_tokens,
-                  (int64_t)tokens, tok_off);
-    SBX_LAUNCH_CHECK(h);
-  }
+  unsigned *line_off = nullptr, *tok_off = nullptr;
+  SBX_TRY(tl_lines_and_tokens(h, text, bytes, &lines, &tokens, &line_off, &tok_off));
   // (2) per line: first token, entries, comment; scans: first entry and vertex of every line
   unsigned *line_tok = nullptr, *line_ent = nullptr, *line_ncb = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_tok));
@@ -508,20 +404,11 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
 template <typename RP, typename CI>
 static int gr_format_typed(sbx_handle_t h, GrJob job, void *text_out, int64_t capacity, int64_t *bytes_host) {
   // the ends of the range, and that the offsets between them ascend (the item search relies on it)
-  int64_t *ends = nullptr;
-  unsigned *descending = nullptr;
-  SBX_TRY(sbx_salloc(h, 2, &ends));
-  SBX_TRY(sbx_salloc(h, 1, &descending));
-  SBX_HIP(h, hipMemsetAsync(descending, 0, sizeof(unsigned), h->stream));
   const int64_t rows = job.re - job.rb;
-  SBX_KLAUNCH(h, SBX_K_TEXT_CHECK, k_gr_range_ends<RP>, dim3(tx_grid(rows)), dim3(TX_THREADS), (const RP *)job.rp, job.rb,
-              job.re, ends, descending);
-  SBX_LAUNCH_CHECK(h);
   int64_t hends[2] = {0, 0};
-  unsigned hdesc = 0;
-  SBX_TRY(sbx_readback(h, hends, ends, sizeof(hends)));
-  SBX_TRY(sbx_readback(h, &hdesc, descending, sizeof(unsigned)));
-  if (hdesc || hends[0] < 0) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: row_ptr descends inside the row range");
+  bool hdesc = false;
+  SBX_TRY(tx_range_ends<RP>(h, (const RP *)job.rp, job.rb, job.re, hends, &hdesc));
+  if (hdesc) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: row_ptr descends inside the row range");
   const int64_t entries = hends[1] - hends[0];
   job.e0 = hends[0];
   job.items = entries + rows * (int64_t)(1 + job.nvw) + 1;
@@ -595,9 +482,7 @@ extern "C" int sbgr_metis_format(sbx_handle_t h, sbx_index_type it, sbx_value_ty
   job.vw = vw ? 1 : 0;
   job.vb = vbytes;
   job.precision = precision;
-  job.vkind = (vt == SBX_V_F32 || vt == SBX_V_F64) ? GV_RECORD
-              : (vt == SBX_V_I32 || vt == SBX_V_I64) ? GV_SIGNED
-              : vt == SBX_V_NONE ? GV_NONE : GV_UNSIGNED;
+  job.vkind = tx_item_kind(vt);
   if (it == SBX_I64) return gr_format_typed<int64_t, int64_t>(h, job, text_out, capacity, bytes_host);
   if (it == SBX_I32_N64) return gr_format_typed<int64_t, int32_t>(h, job, text_out, capacity, bytes_host);
   return gr_format_typed<int32_t, int32_t>(h, job, text_out, capacity, bytes_host);

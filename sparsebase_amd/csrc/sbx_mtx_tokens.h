@@ -1,7 +1,7 @@
 // sbx_mtx_tokens.h — the tokenizer of the text parsers: whitespace-separated tokens of a device text buffer, their
 // starts counted per tile and compacted in file order (count, scan, write).  Shared by the coordinate / edge-list
-// parsers (sbx_mtx.hip), the array-format parser (sbx_dense.hip) and the METIS graph parser (sbx_metis.hip), with the
-// conversion of a value token that the three share.
+// parsers (sbx_mtx.hip), the array-format parser (sbx_dense.hip) and the METIS graph and PaToH parsers (sbx_metis.hip,
+// sbx_patoh.hip), with the conversion of a value token that the first three share.
 #pragma once
 #include "sbx_dec2bin.h"
 #include "sbx_device.h"

@@ -1,6 +1,6 @@
 // sbx_text_emit.h — what the text formatters share: integer printing, floating-point values -> decimal records
 // (sbx_bin2dec.h) and the write-out of a workgroup's LDS text image in aligned 16-byte words.  Used by the Matrix Market /
-// edge-list formatters (sbx_text.hip) and the METIS graph formatter (sbx_metis.hip).
+// edge-list formatters (sbx_text.hip), the METIS graph formatter (sbx_metis.hip) and the PaToH formatters (sbx_patoh.hip).
 #pragma once
 #include "sbx_bin2dec.h"
 #include "sbx_device.h"
@@ -22,6 +22,27 @@ __device__ __forceinline__ int tx_emit_signed(int64_t v, char *dst) {
     return 1 + sbx_b2d::emit_u64(0ull - (uint64_t)v, dst + 1);
   }
   return sbx_b2d::emit_u64((uint64_t)v, dst);
+}
+
+// ---- a value of the formatters' items: how it is kept (vkind) and its text.  TI_RECORD: floating point, printed from the
+// decimal record rec[irel] (tx_records); the integer kinds print arr[i], a value of vb bytes, in full
+enum : int { TI_NONE = 0, TI_SIGNED, TI_UNSIGNED, TI_RECORD };
+static inline int tx_item_kind(sbx_value_type vt) {
+  return (vt == SBX_V_F32 || vt == SBX_V_F64) ? TI_RECORD
+         : (vt == SBX_V_I32 || vt == SBX_V_I64) ? TI_SIGNED
+         : vt == SBX_V_NONE ? TI_NONE : TI_UNSIGNED;
+}
+__device__ __forceinline__ int tx_item_value_length(int vkind, int vb, int precision, const void *arr, const sbx_decrec *rec,
+                                               int64_t i, int64_t irel) {
+  if (vkind == TI_RECORD) return sbx_b2d::text_length(rec[irel], precision);
+  if (vkind == TI_SIGNED) return tx_len_signed(vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i]);
+  return sbx_b2d::length_u64(vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i]);
+}
+__device__ __forceinline__ int tx_item_value_emit(int vkind, int vb, int precision, const void *arr, const sbx_decrec *rec,
+                                             int64_t i, int64_t irel, char *dst) {
+  if (vkind == TI_RECORD) return sbx_b2d::emit(rec[irel], precision, dst);
+  if (vkind == TI_SIGNED) return tx_emit_signed(vb == 4 ? (int64_t)((const int32_t *)arr)[i] : ((const int64_t *)arr)[i], dst);
+  return sbx_b2d::emit_u64(vb == 4 ? (uint64_t)((const uint32_t *)arr)[i] : ((const uint64_t *)arr)[i], dst);
 }
 
 // ---- values -> decimal records
@@ -88,6 +109,35 @@ __device__ __forceinline__ void tx_block_store(const char *s_text, unsigned phas
 }
 
 static unsigned tx_grid(int64_t count) { return (unsigned)((count + TX_THREADS - 1) / TX_THREADS); }
+
+// the offsets of a row range's ends; whether the offsets of the range descend somewhere (the formatters over CSR rows
+// search their items in the offsets, which relies on their order)
+template <typename T>
+__global__ __launch_bounds__(TX_THREADS) void k_tx_range_ends(const T *__restrict__ rp, int64_t rb, int64_t re,
+                                                              int64_t *__restrict__ ends, unsigned *__restrict__ descending) {
+  const int64_t r = rb + (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  if (r == rb) {
+    ends[0] = (int64_t)rp[rb];
+    ends[1] = (int64_t)rp[re];
+  }
+  if (r < re && rp[r + 1] < rp[r]) atomicOr(descending, 1u);
+}
+// (the read-back of both: *desc_host is set where the range cannot be formatted; the caller has begun the arena)
+template <typename T>
+static int tx_range_ends(sbx_handle_t h, const T *rp, int64_t rb, int64_t re, int64_t ends_host[2], bool *desc_host) {
+  int64_t *ends = nullptr;
+  unsigned *descending = nullptr;
+  SBX_TRY(sbx_salloc(h, 2, &ends));
+  SBX_TRY(sbx_salloc(h, 1, &descending));
+  SBX_HIP(h, hipMemsetAsync(descending, 0, sizeof(unsigned), h->stream));
+  SBX_KLAUNCH(h, SBX_K_TEXT_CHECK, k_tx_range_ends<T>, dim3(tx_grid(re - rb)), dim3(TX_THREADS), rp, rb, re, ends, descending);
+  SBX_LAUNCH_CHECK(h);
+  unsigned hdesc = 0;
+  SBX_TRY(sbx_readback(h, ends_host, ends, 2 * sizeof(int64_t)));
+  SBX_TRY(sbx_readback(h, &hdesc, descending, sizeof(unsigned)));
+  *desc_host = hdesc != 0 || ends_host[0] < 0;
+  return SBX_OK;
+}
 
 // the decimal records of `count` floating-point values of vb bytes (steps 1 and 2 of a formatter): the 128-bit fast path,
 // then the listed values through the multi-limb path; the caller has begun the arena

@@ -1,8 +1,14 @@
-// sparsebase/object/object.h — Object, AbstractObject and Graph (reference: object/object.h:28-73, object/object.cc:12-158):
-// a connectivity Format held with or without ownership, and for a Graph its dimensions, the number of vertex weights and
-// the per-vertex weight arrays, all public as in the reference.  The connectivity may be a host or a device format.
+// sparsebase/object/object.h — Object, AbstractObject, Graph and HyperGraph (reference: object/object.h:28-87,
+// object/object.cc:12-158): a connectivity Format held with or without ownership, and for a Graph its dimensions, the
+// number of vertex weights and the per-vertex weight arrays, all public as in the reference.  The connectivity may be a
+// host or a device format.
 //
-// Not here: HyperGraph (its reader and writer are not part of this layer yet).
+// HyperGraph is a Graph whose connectivity is the nets x cells CSR (n_ nets, m_ pins: the pins of a net in file order, in
+// the file's base), with the cells x nets CSR beside it (xNetCSR_), the weights of the nets and of the cells, the base
+// the ids are in and the number of constraints: the reference's two constructors and public members.  One member more:
+// xNetHIPCSR_, the cells x nets side of a hypergraph that PatohReader::ReadHIPHyperGraph left on the device (xNetCSR_ is
+// null there).  What a reader allocates — the cells x nets CSR and the two weight arrays — is owned by the HyperGraph it
+// returns (OwnParts) and freed with it; a HyperGraph constructed from a caller's parts does not own them.
 //
 // One thing more than the reference: the weight arrays that MetisGraphReader::ReadGraph allocates are owned by the Graph
 // it returns (OwnVertexWeights) and freed with it; the reference leaks them.  A Graph constructed from a caller's
@@ -12,12 +18,14 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sparsebase/format/array.h"
 #include "sparsebase/format/coo.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/format.h"
+#include "sparsebase/format/hip_formats.h"
 
 namespace sparsebase::io {
 template <typename I, typename N, typename V>
@@ -136,6 +144,44 @@ class Graph : public AbstractObject<VertexID, NumEdges, Weight> {
     InitializeInfoFromConnection();
   }
   std::function<void()> release_weights_;
+};
+
+template <typename VertexID, typename NumEdges, typename Weight>
+class HyperGraph : public Graph<VertexID, NumEdges, Weight> {
+ public:
+  HyperGraph() = default;
+  HyperGraph(format::Format *connectivity, VertexID base_type, VertexID constraint_num,
+             format::CSR<VertexID, NumEdges, Weight> *xNetCSR)
+      : Graph<VertexID, NumEdges, Weight>(connectivity), constraint_num_(constraint_num), base_type_(base_type),
+        xNetCSR_(xNetCSR) {}
+  HyperGraph(format::Format *connectivity, format::Array<Weight> *netWeights, format::Array<Weight> *cellWeights,
+             VertexID base_type, VertexID constraint_num, format::CSR<VertexID, NumEdges, Weight> *xNetCSR)
+      : Graph<VertexID, NumEdges, Weight>(connectivity), constraint_num_(constraint_num), base_type_(base_type),
+        xNetCSR_(xNetCSR), netWeights_(netWeights), cellWeights_(cellWeights) {}
+  HyperGraph(const HyperGraph &) = delete;  // (the parts are raw pointers: a copy would share or leak them)
+  HyperGraph &operator=(const HyperGraph &) = delete;
+  ~HyperGraph() override {
+    if (!owns_parts_) return;
+    delete xNetCSR_;
+    delete xNetHIPCSR_;
+    if constexpr (!std::is_same_v<Weight, void>) {
+      delete netWeights_;
+      delete cellWeights_;
+    }
+  }
+  // the HyperGraph frees xNetCSR_ / xNetHIPCSR_ and the two weight arrays when it dies (what a reader allocated for it)
+  void OwnParts() { owns_parts_ = true; }
+  bool PartsAreOwned() const { return owns_parts_; }
+
+  VertexID constraint_num_ = 1;
+  VertexID base_type_ = 0;
+  format::CSR<VertexID, NumEdges, Weight> *xNetCSR_ = nullptr;
+  format::Array<Weight> *netWeights_ = nullptr;
+  format::Array<Weight> *cellWeights_ = nullptr;
+  format::HIPCSR<VertexID, NumEdges, Weight> *xNetHIPCSR_ = nullptr;
+
+ private:
+  bool owns_parts_ = false;
 };
 
 }  // namespace sparsebase::object

@@ -37,6 +37,8 @@
 #include "sparsebase/bases/iobase.h"
 #include "sparsebase/io/metis_graph_reader.h"
 #include "sparsebase/io/metis_graph_writer.h"
+#include "sparsebase/io/patoh_reader.h"
+#include "sparsebase/io/patoh_writer.h"
 #include "sparsebase/object/object.h"
 
 namespace sparsebase {

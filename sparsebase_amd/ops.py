@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -785,3 +785,62 @@ def metis_format(row_ptr, col, val=None, vwgt=None, row_begin=0, row_end=None, i
     return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbgr_metis_format(
         hd.h, _it(row_ptr, col), vt, row_begin, row_end, _p(row_ptr), _p(col), _p(val), _p(vwgt), ncon, index_base,
         precision, flags, out, cap, C.byref(nb)))
+
+
+# ----------------------------------------------------------------------------- PaToH hypergraph files (include/sbhg.h)
+def patoh_parse(text, cells, nets, pins, base=0, scheme=0, index_dtype=torch.int32, value_dtype=None, offset_dtype=None,
+                transpose=True):
+    """text: uint8 device tensor with the bytes after the header line; cells, nets, pins, base, scheme as
+    sparsebase_amd.patoh.parse_header gives them.  Returns (xpin, pin, xnet, net, net_wgt, cell_wgt): the nets x cells CSR
+    in file order and file base, the cells x nets CSR (None with transpose=False) and the weights (None unless value_dtype
+    is given; 1 where the file has none) (sbhg_patoh_parse)."""
+    dev = _check_dev(text)
+    hd = handle_for(dev)
+    offset_dtype = index_dtype if offset_dtype is None else offset_dtype
+    it = _it(torch.empty(0, dtype=offset_dtype), torch.empty(0, dtype=index_dtype))
+    xpin = torch.empty(max(0, nets) + 1, dtype=offset_dtype, device=dev)
+    pin = torch.empty(max(1, pins), dtype=index_dtype, device=dev)
+    xnet = torch.empty(max(0, cells) + 1, dtype=offset_dtype, device=dev) if transpose else None
+    net = torch.empty(max(1, pins), dtype=index_dtype, device=dev) if transpose else None
+    nw = torch.empty(max(0, nets), dtype=value_dtype, device=dev) if value_dtype is not None else None
+    cw = torch.empty(max(0, cells), dtype=value_dtype, device=dev) if value_dtype is not None else None
+    vt = capi.V_NONE if value_dtype is None else _VT[value_dtype]
+    counts = (C.c_int64 * 3)()
+    hd.check(hd.lib.sbhg_patoh_parse(hd.h, it, vt, _p(text), text.numel(), cells, nets, pins, base, scheme, max(1, pins),
+                                     _p(xpin), _p(pin), _p(xnet), _p(net), _p(nw), _p(cw), counts))
+    return xpin, pin[:pins], xnet, (None if net is None else net[:pins]), nw, cw
+
+
+def cells_to_nets(xpin, pin, cells, base=0):
+    """(xnet, net) of the nets x cells CSR (xpin, pin): row c lists, in ascending pin position, the net (+ base) of every
+    pin equal to c + base (sbhg_cells_to_nets)."""
+    dev = _check_dev(xpin, pin)
+    hd = handle_for(dev)
+    xnet = torch.empty(cells + 1, dtype=xpin.dtype, device=dev)
+    net = torch.empty(pin.numel(), dtype=pin.dtype, device=dev)
+    hd.check(hd.lib.sbhg_cells_to_nets(hd.h, _it(xpin, pin), cells, xpin.numel() - 1, _p(xpin), _p(pin), base, _p(xnet),
+                                       _p(net)))
+    return xnet, net
+
+
+def patoh_format(xpin, pin, net_wgt=None, net_begin=0, net_end=None, index_delta=0, precision=6, net_weights=False,
+                 last_newline=True, unsigned=False):
+    """The lines of nets [net_begin, net_end) as PatohWriter writes them, a uint8 device tensor (sbhg_patoh_format)."""
+    dev = _check_dev(xpin, pin, net_wgt)
+    hd = handle_for(dev)
+    net_end = xpin.numel() - 1 if net_end is None else net_end
+    vt = capi.V_NONE if net_wgt is None else _text_vt(net_wgt, unsigned)
+    flags = (capi.HG_NET_WEIGHTS if net_weights else 0) | (0 if last_newline else capi.HG_NO_LAST_NEWLINE)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbhg_patoh_format(
+        hd.h, _it(xpin, pin), vt, net_begin, net_end, _p(xpin), _p(pin), _p(net_wgt), index_delta, precision, flags, out,
+        cap, C.byref(nb)))
+
+
+def patoh_format_weights(wgt, begin=0, end=None, precision=6, unsigned=False):
+    """The cell-weight line: wgt[begin:end] joined by single blanks, a uint8 device tensor (sbhg_patoh_format_weights)."""
+    dev = _check_dev(wgt)
+    hd = handle_for(dev)
+    end = wgt.numel() if end is None else end
+    vt = _text_vt(wgt, unsigned)
+    return _text_two_calls(hd, dev, lambda out, cap, nb: hd.lib.sbhg_patoh_format_weights(
+        hd.h, vt, begin, end, _p(wgt), precision, out, cap, C.byref(nb)))
