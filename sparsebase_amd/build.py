@@ -33,6 +33,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbio.h"))
     hs.append(os.path.join(ROOT, "include", "sbgr.h"))
     hs.append(os.path.join(ROOT, "include", "sbhg.h"))
+    hs.append(os.path.join(ROOT, "include", "sbfx.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

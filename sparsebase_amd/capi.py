@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h and
-include/sbhg.h
+"""ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
+include/sbhg.h and include/sbfx.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -173,6 +173,13 @@ HYPERGRAPH_PROTOTYPES = {
     "sbhg_patoh_format_weights": ([_H, _int, _i64, _i64, _vp, _int, _vp, _i64, C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbfx.h declares (tests/test_extract_abi.py checks header <-> library <-> this table): the fused
+# feature classes, prefix `sbfx_`
+EXTRACT_PROTOTYPES = {
+    "sbfx_csr_degrees_degree_distribution": ([_H, _int, _i64, _i64, _vp, _int, _vp, _vp], _int),
+    "sbfx_csr_bandwidth_profile": ([_H, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -186,7 +193,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
-                                           list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items())):
+                                           list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
+                                           list(EXTRACT_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -5,12 +5,15 @@
 //   feature/degree_distribution.cc:152-167  sbx_csr_degree_distribution
 //   feature/bandwidth.cc:93-112             sbx_csr_bandwidth
 //   feature/profile.cc:91-105               sbx_csr_profile
+//   feature/degrees_degree_distribution.cc:146-164   sbfx_csr_degrees_degree_distribution (include/sbfx.h)
+//   the second and the fourth of the above in one pass  sbfx_csr_bandwidth_profile        (include/sbfx.h)
 //
 // All four are single-pass reductions.  Bandwidth and profile are nonzero-parallel so
 // power-law rows stay balanced: the row of every nonzero is derived per tile from row_ptr
 // (tile_rows), never from a per-row loop.
 #include <type_traits>
 
+#include "sbfx.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
 
@@ -172,6 +175,80 @@ __global__ __launch_bounds__(FT_THREADS) void k_profile_csr(const I *__restrict_
   if (tid == 0) {
     for (int w = 1; w < FT_THREADS / 64; w++) sum += s_sum[w];
     if (sum) atomicAdd(&partial[blockIdx.x & (FT_SLOTS - 1)], sum);
+  }
+}
+
+// ---- the fused passes of include/sbfx.h ------------------------------------------------------------------------------
+// k_degrees and k_degree_distribution in one read of row_ptr (degrees_degree_distribution.cc:155-158): a row per thread
+// and grid stride, as the two are, so the loads and both stores of a wave are contiguous whatever the pointers'
+// alignment; the division is the one of k_degree_distribution
+template <typename I, typename D, typename F>
+__global__ __launch_bounds__(FT_THREADS) void k_degrees_degree_distribution(const I *__restrict__ rp, D *__restrict__ deg,
+                                                                            F *__restrict__ dist, int64_t n, F nnz) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const I d = rp[i + 1] - rp[i];
+    deg[i] = (D)d;
+    dist[i] = (F)d / nnz;
+  }
+}
+
+// k_bandwidth_csr and k_profile_csr in one read of the columns and one tile_rows per tile: every entry feeds
+// max |row - col|, a row's head entry the profile sum, every other entry the sortedness flag
+template <typename I, typename P>
+__global__ __launch_bounds__(FT_THREADS) void k_bandwidth_profile_csr(const I *__restrict__ rp, const I *__restrict__ col,
+                                                                      int64_t n, int64_t nnz, P *__restrict__ pmax,
+                                                                      unsigned long long *__restrict__ psum,
+                                                                      int *__restrict__ unsorted, bool vec_ok,
+                                                                      const int2 *__restrict__ span) {
+  __shared__ int s_head[FT_TILE];
+  __shared__ int s_wmax[FT_THREADS / 64];
+  __shared__ P s_mx[FT_THREADS / 64];
+  __shared__ unsigned long long s_sum[FT_THREADS / 64];
+  const int tid = threadIdx.x;
+  const int64_t tiles = (nnz + FT_TILE - 1) / FT_TILE;
+  P mx = 0;
+  unsigned long long sum = 0;
+  bool bad = false;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {  // (one tile per workgroup as launched)
+    const int64_t t0 = tile * FT_TILE;
+    const int64_t t1 = (t0 + FT_TILE < nnz) ? t0 + FT_TILE : nnz;
+    const int64_t base = t0 + (int64_t)tid * FT_ITEMS;
+    I c[FT_ITEMS + 1];  // c[0]: the nonzero before this thread's first one
+    c[0] = base > 0 ? col[base - 1 < t1 ? base - 1 : t1 - 1] : 0;
+    sbx_load_items8(col, base, t1, vec_ok, c + 1);
+    const TileRows t = tile_rows(rp, span, tile, t0, s_head, s_wmax);
+#pragma unroll
+    for (int k = 0; k < FT_ITEMS; k++) {
+      if (base + k < t1) {
+        const int64_t d = t.r_lo + t.h[k] - (int64_t)c[k + 1];
+        const P a = (P)(d < 0 ? -d : d);
+        mx = a > mx ? a : mx;
+        if (t.head[k]) {
+          if (d > 0) sum += (unsigned long long)d;
+        } else {
+          bad |= c[k + 1] < c[k];
+        }
+      }
+    }
+    __syncthreads();  // the LDS of tile_rows is reused
+  }
+  if (__any(bad) && sbx_lane() == 0) *unsorted = 1;
+  mx = sbx_wave_max(mx);
+  sum = sbx_wave_sum(sum);
+  if (sbx_lane() == 0) {
+    s_mx[sbx_wave_in_block()] = mx;
+    s_sum[sbx_wave_in_block()] = sum;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < FT_THREADS / 64; w++) {
+      mx = s_mx[w] > mx ? s_mx[w] : mx;
+      sum += s_sum[w];
+    }
+    if (mx) atomicMax(&pmax[blockIdx.x & (FT_SLOTS - 1)], mx);  // (FT_SLOTS result words: see k_bandwidth_csr)
+    if (sum) atomicAdd(&psum[blockIdx.x & (FT_SLOTS - 1)], sum);
   }
 }
 
@@ -436,4 +513,123 @@ extern "C" int sbx_csr_profile(sbx_handle_t h, sbx_index_type it, int64_t n, int
   *profile_host = 0;
   return it == SBX_I64 ? csr_profile_typed<int64_t>(h, n, nnz, row_ptr, col, profile_host)
                        : csr_profile_typed<int32_t>(h, n, nnz, row_ptr, col, profile_host);
+}
+
+// ---- include/sbfx.h ---------------------------------------------------------------------------------------------------
+template <typename I, typename D>
+static int csr_degrees_degree_distribution_typed(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr,
+                                                 int feature_bytes, void *degrees_out, void *dist_out) {
+  SBX_TRY(sbx_arena_begin(h));
+  if (n == 0) return SBX_OK;
+  const unsigned grid = sbx_grid_for(n, FT_THREADS, 8192);
+  if (feature_bytes == 4)
+    SBX_KLAUNCH(h, SBX_K_FEATURE, (k_degrees_degree_distribution<I, D, float>), dim3(grid), dim3(FT_THREADS),
+                (const I *)row_ptr, (D *)degrees_out, (float *)dist_out, n, (float)nnz);
+  else
+    SBX_KLAUNCH(h, SBX_K_FEATURE, (k_degrees_degree_distribution<I, D, double>), dim3(grid), dim3(FT_THREADS),
+                (const I *)row_ptr, (D *)degrees_out, (double *)dist_out, n, (double)nnz);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_FEATURE, ((int64_t)sizeof(I) + (int64_t)sizeof(D) + feature_bytes) * n + (int64_t)sizeof(I));
+  return SBX_OK;
+}
+
+extern "C" int sbfx_csr_degrees_degree_distribution(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz,
+                                                    const void *row_ptr, int feature_bytes, void *degrees_out,
+                                                    void *dist_out) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, n >= 0 && nnz >= 0 && row_ptr && (n == 0 || (degrees_out && dist_out)), "bad argument");
+  SBX_REQUIRE(h, feature_bytes == 4 || feature_bytes == 8, "feature type must be float or double");
+  if (it == SBX_I32_N64)
+    return csr_degrees_degree_distribution_typed<int64_t, int32_t>(h, n, nnz, row_ptr, feature_bytes, degrees_out, dist_out);
+  return it == SBX_I64
+             ? csr_degrees_degree_distribution_typed<int64_t, int64_t>(h, n, nnz, row_ptr, feature_bytes, degrees_out, dist_out)
+             : csr_degrees_degree_distribution_typed<int32_t, int32_t>(h, n, nnz, row_ptr, feature_bytes, degrees_out, dist_out);
+}
+
+// the general path of csr_profile_typed (which stays as it is) for the fused call: the smallest column of every row
+// through expand_rows, k_row_min_col and k_profile; the caller holds the arena and a NestGuard
+template <typename I>
+static int profile_of_unsorted_rows(sbx_handle_t h, int64_t n, int64_t nnz, const I *row_ptr, const I *col,
+                                    int64_t *profile_host) {
+  const unsigned grid_n = sbx_grid_for(n, FT_THREADS, (int64_t)h->num_cus * 8);
+  unsigned long long *partial = nullptr;
+  FeatureAcc *acc = nullptr;
+  I *rows = nullptr, *rowmin = nullptr;
+  SBX_TRY(sbx_salloc(h, grid_n, &partial));
+  SBX_TRY(sbx_salloc(h, 1, &acc));
+  SBX_TRY(expand_rows<I>(h, n, nnz, row_ptr, &rows));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &rowmin));
+  SBX_KLAUNCH(h, SBX_K_FEATURE, k_iota<I>, dim3(grid_n), dim3(FT_THREADS), rowmin, n);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, k_row_min_col<I>, dim3((unsigned)((nnz + FT_TILE - 1) / FT_TILE)), dim3(FT_THREADS),
+              (const I *)rows, col, nnz, rowmin);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, k_profile<I>, dim3(grid_n), dim3(FT_THREADS), (const I *)rowmin, n, partial);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, k_feature_finish<unsigned>, dim3(1), dim3(FT_THREADS), (const unsigned *)nullptr,
+              (const unsigned long long *)partial, (int)grid_n, acc);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_FEATURE, (int64_t)sizeof(I) * (nnz + n + 1));
+  FeatureAcc ha;
+  SBX_TRY(sbx_readback(h, &ha, acc, sizeof(FeatureAcc)));
+  *profile_host = (int64_t)ha.profile;
+  return SBX_OK;
+}
+
+template <typename I>
+static int csr_bandwidth_profile_typed(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, const void *col,
+                                       int64_t *bandwidth_host, int64_t *profile_host) {
+  typedef typename std::conditional<sizeof(I) == 4, unsigned, unsigned long long>::type P;
+  SBX_TRY(sbx_arena_begin(h));
+  if (nnz == 0 || n == 0) return SBX_OK;  // both stay 0 without nonzeros
+  NestGuard guard(h);
+  const int64_t tiles = (nnz + FT_TILE - 1) / FT_TILE;
+  const unsigned grid = FT_SLOTS;
+  // one block, zeroed once: the profile's result words, FeatureAcc and the sortedness flag, the bandwidth's result words
+  struct { FeatureAcc a; int unsorted; int pad; } hs;
+  unsigned long long *psum = nullptr;
+  SBX_TRY(sbx_salloc(h, 2 * grid + 3, &psum));
+  unsigned long long *res = psum + grid;
+  P *pmax = (P *)(res + 3);
+  SBX_HIP(h, hipMemsetAsync(psum, 0, (2 * grid + 3) * sizeof(unsigned long long), h->stream));
+  int2 *span = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)tiles, &span));
+  SBX_KLAUNCH(h, SBX_K_FEATURE, (k_tile_spans<I, FT_TILE, FT_THREADS>),
+              dim3((unsigned)((tiles + FT_THREADS - 1) / FT_THREADS)), dim3(FT_THREADS), (const I *)row_ptr, n, nnz, tiles,
+              span);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, (k_bandwidth_profile_csr<I, P>), dim3((unsigned)tiles), dim3(FT_THREADS),
+              (const I *)row_ptr, (const I *)col, n, nnz, pmax, psum, (int *)(res + 2), ((uintptr_t)col & 15) == 0,
+              (const int2 *)span);
+  SBX_KLAUNCH(h, SBX_K_FEATURE, k_feature_finish<P>, dim3(1), dim3(FT_THREADS), (const P *)pmax,
+              (const unsigned long long *)psum, (int)grid, (FeatureAcc *)res);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_FEATURE, (int64_t)sizeof(I) * (nnz + n + 1));
+  SBX_TRY(sbx_readback(h, &hs, res, sizeof(hs)));
+  *bandwidth_host = (int64_t)hs.a.max_dist + 1;
+  if (!hs.unsorted) {
+    *profile_host = (int64_t)hs.a.profile;
+    return SBX_OK;
+  }
+  return profile_of_unsorted_rows<I>(h, n, nnz, (const I *)row_ptr, (const I *)col, profile_host);
+}
+
+extern "C" int sbfx_csr_bandwidth_profile(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t nnz, const void *row_ptr,
+                                          const void *col, int64_t *bandwidth_host, int64_t *profile_host) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, n >= 0 && nnz >= 0 && row_ptr && bandwidth_host && profile_host && (nnz == 0 || col), "bad argument");
+  if (it == SBX_I32_N64) {  // the way of sbx_mixed_csr_bandwidth: 32-bit offsets inside
+    if (nnz >= ((int64_t)1 << 31))
+      SBX_FAIL(h, SBX_ERR_UNSUPPORTED,
+               "sbfx_csr_bandwidth_profile: 64-bit offsets with nnz >= 2^31 (the offsets inside this operation are 32-bit)");
+    int *ovf = nullptr;
+    int32_t *rp = nullptr;
+    SBX_TRY(sbx_i64_begin(h, &ovf));
+    int rc = sbx_narrow_i64(h, row_ptr, n + 1, &rp, ovf);
+    if (rc == SBX_OK) rc = sbfx_csr_bandwidth_profile(h, SBX_I32, n, nnz, rp, col, bandwidth_host, profile_host);
+    sbx_i64_end(h);
+    return rc;
+  }
+  SBX_REQUIRE(h, n < ((int64_t)1 << 31) - 1 && (it == SBX_I64 || nnz < ((int64_t)1 << 31)) &&
+                     nnz / FT_TILE < ((int64_t)1 << 31), "dimension exceeds what the index type holds");
+  *bandwidth_host = 0;
+  *profile_host = 0;
+  return it == SBX_I64 ? csr_bandwidth_profile_typed<int64_t>(h, n, nnz, row_ptr, col, bandwidth_host, profile_host)
+                       : csr_bandwidth_profile_typed<int32_t>(h, n, nnz, row_ptr, col, bandwidth_host, profile_host);
 }

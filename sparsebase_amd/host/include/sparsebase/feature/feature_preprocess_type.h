@@ -11,6 +11,10 @@
 
 namespace sparsebase::feature {
 
+// the params of the fused classes (the reference defines it in min_max_avg_degree.h:12 and again in
+// degrees_degree_distribution.h:12)
+struct Params : utils::Parameters {};
+
 template <typename FeatureType>
 class FeaturePreprocessType : public utils::FunctionMatcherMixin<FeatureType, utils::Extractable> {
  public:
@@ -25,6 +29,10 @@ class FeaturePreprocessType : public utils::FunctionMatcherMixin<FeatureType, ut
     if (std::find(ids.begin(), ids.end(), t) == ids.end())
       throw utils::FeatureParamsException(get_id().name(), t.name());
     this->pmap_[t] = p;
+    // the object's own params are what Execute runs with: this is how the params of an added feature reach the
+    // registered instance feature::Extractor runs in its place (the reference updates the map alone and runs a
+    // registered single class with its default params)
+    if (t == get_id()) this->params_ = p;
   }
   std::type_index get_id() override { return typeid(*this); }
   ~FeaturePreprocessType() override = default;

@@ -12,8 +12,6 @@
 
 namespace sparsebase::feature {
 
-struct Params : utils::Parameters {};
-
 template <typename IDType, typename NNZType, typename ValueType, typename FeatureType>
 class MinMaxAvgDegree : public FeaturePreprocessType<std::unordered_map<std::type_index, std::any>> {
   typedef MinDegree<IDType, NNZType, ValueType> Min;

@@ -2,6 +2,7 @@
 #ifndef SPARSEBASE_SPARSEBASE_H_
 #define SPARSEBASE_SPARSEBASE_H_
 #include "sparsebase/bases/reorder_base.h"
+#include "sparsebase/bases/graph_feature_base.h"
 #include "sparsebase/context/cpu_context.h"
 #include "sparsebase/context/hip_context.h"
 #include "sparsebase/converter/converter_order_one.h"
@@ -10,9 +11,13 @@
 #include "sparsebase/feature/avg_degree.h"
 #include "sparsebase/feature/avg_degree_column.h"
 #include "sparsebase/feature/bandwidth.h"
+#include "sparsebase/feature/bandwidth_profile.h"
 #include "sparsebase/feature/coefficient_of_variation_degree_column.h"
 #include "sparsebase/feature/degree_distribution.h"
 #include "sparsebase/feature/degrees.h"
+#include "sparsebase/feature/degrees_degree_distribution.h"
+#include "sparsebase/feature/extractor.h"
+#include "sparsebase/feature/feature_extractor.h"
 #include "sparsebase/feature/geometric_avg_degree_column.h"
 #include "sparsebase/feature/jaccard_weights.h"
 #include "sparsebase/feature/max_degree.h"

@@ -1,15 +1,17 @@
 // Type identity, once-settable members and small helpers of the host layer
-// (counterpart of the reference's utils/utils.h:130-199).
+// (counterpart of the reference's utils/utils.h:130-230).
 #ifndef SPARSEBASE_UTILS_UTILS_H_
 #define SPARSEBASE_UTILS_UTILS_H_
 #include <cxxabi.h>
 
+#include <any>
 #include <cstdlib>
 #include <limits>
 #include <string>
 #include <type_traits>
 #include <typeindex>
 #include <typeinfo>
+#include <utility>
 #include <vector>
 
 #include "sparsebase/config.h"
@@ -94,6 +96,32 @@ ToType *ConvertArrayType(FromType *from, SizeType size) {
     return to;
   }
 }
+
+// An object of any concrete class behind `Interface`, held by value (utils.h:202-230; feature::Feature is
+// Implementation<Extractable>): constructed from a concrete object it owns a copy of it, copies copy that object, moves
+// move it, and operator-> reaches it through the interface.  A default-constructed one holds nothing and must not be
+// dereferenced.
+template <typename Interface>
+struct Implementation {
+ public:
+  Implementation() = default;
+  template <typename ConcreteType,
+            typename = std::enable_if_t<!std::is_same_v<std::decay_t<ConcreteType>, Implementation>>>
+  explicit Implementation(ConcreteType &&object)
+      : storage_(std::forward<ConcreteType>(object)), access_([](std::any &held) -> Interface & {
+          return std::any_cast<std::decay_t<ConcreteType> &>(held);
+        }) {}
+  Implementation(const Implementation &) = default;
+  Implementation(Implementation &&) noexcept = default;
+  Implementation &operator=(const Implementation &) = default;
+  Implementation &operator=(Implementation &&) noexcept = default;
+
+  Interface *operator->() { return &access_(storage_); }
+
+ private:
+  std::any storage_;
+  Interface &(*access_)(std::any &) = nullptr;
+};
 
 }  // namespace sparsebase::utils
 #endif

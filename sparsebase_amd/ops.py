@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -312,6 +312,33 @@ def csr_profile(row_ptr, col):
     hd.check(hd.lib.sbx_csr_profile(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, col.numel(), _p(row_ptr), _p(col),
                                     C.byref(out)))
     return out.value
+
+
+def csr_degrees_degree_distribution(row_ptr, nnz, dtype=torch.float32, id_dtype=None, out=None):
+    """Degrees and DegreeDistribution of a CSR in one pass over row_ptr (feature::Degrees_DegreeDistribution): the pair
+    (degrees, distribution), bit for bit what csr_degrees and csr_degree_distribution return.  out=(degrees,
+    distribution) writes into the caller's tensors.  See sbfx_csr_degrees_degree_distribution in include/sbfx.h."""
+    hd = handle_for(_check_dev(row_ptr, *(out or ())))
+    n = row_ptr.numel() - 1
+    if out is None:
+        out = (torch.empty(n, dtype=id_dtype or row_ptr.dtype, device=row_ptr.device),
+               torch.empty(n, dtype=dtype, device=row_ptr.device))
+    deg, dist = out
+    if deg.numel() != n or dist.numel() != n or dist.dtype not in (torch.float32, torch.float64):
+        raise ValueError("out: n degrees of the id type and n float32 / float64 values")
+    hd.check(hd.lib.sbfx_csr_degrees_degree_distribution(hd.h, _it(row_ptr, deg), n, int(nnz), _p(row_ptr),
+                                                         dist.element_size(), _p(deg), _p(dist)))
+    return deg, dist
+
+
+def csr_bandwidth_profile(row_ptr, col):
+    """Bandwidth and Profile of a CSR in one pass over col (feature::Bandwidth_Profile): the pair of ints csr_bandwidth
+    and csr_profile return.  See sbfx_csr_bandwidth_profile in include/sbfx.h."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    bw, pr = C.c_int64(0), C.c_int64(0)
+    hd.check(hd.lib.sbfx_csr_bandwidth_profile(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, col.numel(), _p(row_ptr),
+                                               _p(col), C.byref(bw), C.byref(pr)))
+    return bw.value, pr.value
 
 
 def csr_jaccard_weights(row_ptr, col, dtype=torch.float32):
