@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h and include/sbfx.h
+include/sbhg.h, include/sbfx.h and include/sbsym.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -23,6 +23,7 @@ TEXT_LOWER, TEXT_NO_DIAGONAL, TEXT_PATTERN = 1, 2, 4
 STAT_MEDIAN, STAT_LOG = 1, 2
 GR_ZERO_INDEX, GR_EDGE_WEIGHTS, GR_VERTEX_WEIGHTS = 1, 2, 4
 HG_NET_WEIGHTS, HG_NO_LAST_NEWLINE = 1, 2
+SYM_NO_DIAGONAL, SYM_SKIP_IF_SYMMETRIC = 1, 2
 
 _STATUS = {0: "ok", 1: "bad argument", 2: "no usable HIP device", 3: "HIP runtime error",
            4: "out of device memory", 5: "unsupported type tuple or shape", 6: "internal error"}
@@ -180,6 +181,14 @@ EXTRACT_PROTOTYPES = {
     "sbfx_csr_bandwidth_profile": ([_H, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbsym.h declares (tests/test_sym_abi.py checks header <-> library <-> this table): the pattern
+# symmetrization A + A^T of a CSR, prefix `sbsym_`
+SYM_PROTOTYPES = {
+    "sbsym_csr_missing_mirrors": ([_H, _int, _i64, _i64, _vp, _vp, C.POINTER(_i64)], _int),
+    "sbsym_csr_symmetrize": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _u, _i64, _vp, _vp, _vp, C.POINTER(_i64),
+                              C.POINTER(_i64)], _int),
+}
+
 _lib = None
 
 
@@ -194,7 +203,7 @@ def load():
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
-                                           list(EXTRACT_PROTOTYPES.items())):
+                                           list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

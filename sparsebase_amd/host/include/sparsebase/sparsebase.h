@@ -38,6 +38,7 @@
 #include "sparsebase/reorder/reorder_heatmap.h"
 #include "sparsebase/reorder/slashburn_reorder.h"
 #include "sparsebase/utils/logger.h"
+#include "sparsebase/utils/symmetrize.h"
 // last: the reader needs the complete conversion graph
 #include "sparsebase/bases/iobase.h"
 #include "sparsebase/io/metis_graph_reader.h"

@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -402,9 +402,16 @@ def degree_reorder(row_ptr, ascending=True, out=None, id_dtype=None):
     return inv
 
 
-def rcm_reorder(row_ptr, col, out=None, return_stats=False):
+def rcm_reorder(row_ptr, col, out=None, return_stats=False, symmetrize=False):
+    """symmetrize=True orders the pattern of A + A^T where A is not structurally symmetric (what sbx_rcm_reorder refuses):
+    one sbsym_csr_symmetrize call in pattern mode that leaves a symmetric A alone, then RCM on A or on the symmetrized
+    pattern."""
     hd = handle_for(_check_dev(row_ptr, col))
     n = row_ptr.numel() - 1
+    if symmetrize:
+        rp_s, col_s, _, added = _csr_symmetrize(hd, row_ptr, col, None, capi.SYM_SKIP_IF_SYMMETRIC)
+        if added:
+            row_ptr, col = rp_s, col_s
     inv = torch.empty(n, dtype=col.dtype, device=row_ptr.device) if out is None else out
     stats = capi.RcmStats()
     hd.check(hd.lib.sbx_rcm_reorder(hd.h, _it(row_ptr, col), n, col.numel(), _p(row_ptr), _p(col), _p(inv),
@@ -412,6 +419,39 @@ def rcm_reorder(row_ptr, col, out=None, return_stats=False):
     if return_stats:
         return inv, {k: getattr(stats, k) for k, _ in capi.RcmStats._fields_}
     return inv
+
+
+# ----------------------------------------------------------------------------- A + A^T (include/sbsym.h)
+def csr_missing_mirrors(row_ptr, col):
+    """How many entries a square CSR with column-sorted rows lacks to be structurally symmetric, an int (0: it is).
+    See sbsym_csr_missing_mirrors in include/sbsym.h."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    out = C.c_int64(0)
+    hd.check(hd.lib.sbsym_csr_missing_mirrors(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, col.numel(), _p(row_ptr),
+                                              _p(col), C.byref(out)))
+    return out.value
+
+
+def _csr_symmetrize(hd, row_ptr, col, val, flags):
+    """One sbsym_csr_symmetrize call into 2 * nnz entries of capacity (A + A^T never holds more), trimmed."""
+    nnz = col.numel()
+    cap = max(1, 2 * nnz)
+    rpo = torch.empty_like(row_ptr)
+    co = torch.empty(cap, dtype=col.dtype, device=col.device)
+    vo = None if val is None else torch.empty(cap, dtype=val.dtype, device=val.device)
+    nnz_out, added = C.c_int64(0), C.c_int64(0)
+    hd.check(hd.lib.sbsym_csr_symmetrize(hd.h, _it(row_ptr, col), _vt(val), row_ptr.numel() - 1, nnz, _p(row_ptr), _p(col),
+                                         _p(val), flags, cap, _p(rpo), _p(co), _p(vo), C.byref(nnz_out), C.byref(added)))
+    k = nnz_out.value
+    return rpo, co[:k], (None if vo is None else vo[:k]), added.value
+
+
+def csr_symmetrize(row_ptr, col, val=None, no_diagonal=False):
+    """A + A^T of a square CSR with column-sorted rows: (row_ptr_out, col_out, val_out, added).  Every stored entry stays,
+    with its value; every missing mirror is added once, with the value of the first stored entry it mirrors; values are
+    opaque payloads.  no_diagonal drops the stored (i, i).  See sbsym_csr_symmetrize in include/sbsym.h."""
+    hd = handle_for(_check_dev(row_ptr, col, val))
+    return _csr_symmetrize(hd, row_ptr, col, val, capi.SYM_NO_DIAGONAL if no_diagonal else 0)
 
 
 def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
