@@ -85,15 +85,6 @@ __global__ __launch_bounds__(BT) void k_boba_scatter(const uint32_t *__restrict_
     inv[sorted_v[p]] = (I)p;
 }
 
-}  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-namespace {
-
 template <typename I>
 static int boba_typed(sbx_handle_t h, int64_t nodes64, int64_t nnz, const void *row, const void *col, void *inv_out) {
   SBX_TRY(sbx_arena_begin(h));

@@ -81,12 +81,6 @@ __global__ __launch_bounds__(CV_THREADS) void k_pack_rc(const I *__restrict__ ro
 template <int VB> struct ValT { typedef uint32_t type; };
 template <> struct ValT<8> { typedef uint64_t type; };
 
-struct NestGuard {  // the conversions below call other entry points: keep this call's scratch alive
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
-  ~NestGuard() { h->nest--; }
-};
-
 // hybrid COO sort (below): after the records are grouped by row >> s, the rest of the key — the row's low s bits and
 // the column — fits 32 bits and is sorted per group in LDS
 __global__ __launch_bounds__(CV_THREADS) void k_coo_bucket_keys(const int32_t *__restrict__ row,
@@ -418,11 +412,6 @@ static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // ============================================================================
 // C ABI
 // ============================================================================
-#define SBX_REQUIRE(h, cond, msg)                       \
-  do {                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 template <typename I>
 static int coo_is_sorted_typed(sbx_handle_t h, int64_t nnz, const void *row, const void *col, int *sorted_host,
                                int64_t n = -1, int64_t m = -1, int *in_range_host = nullptr) {

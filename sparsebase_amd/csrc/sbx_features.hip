@@ -330,12 +330,6 @@ __global__ __launch_bounds__(FT_THREADS) void k_feature_finish(const P *__restri
   }
 }
 
-struct NestGuard {
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
-  ~NestGuard() { h->nest--; }
-};
-
 // row ids of every nonzero into scratch (the CSR -> COO move conversion)
 template <typename I>
 int expand_rows(sbx_handle_t h, int64_t n, int64_t nnz, const I *rp, I **rows) {
@@ -345,11 +339,6 @@ int expand_rows(sbx_handle_t h, int64_t n, int64_t nnz, const I *rp, I **rows) {
 }
 
 }  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
 
 #ifndef SBX_DEBUG_DEGREES_STREAM0
 #define SBX_DEBUG_DEGREES_STREAM0 0  // 1: k_degrees goes to the null stream instead of the handle's (the wrong-stream build

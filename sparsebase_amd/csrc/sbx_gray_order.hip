@@ -29,12 +29,6 @@
 
 namespace {
 
-struct NestGuard {  // the nested entry point must not rewind the caller's scratch
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h_) : h(h_) { h->nest++; }
-  ~NestGuard() { if (h->nest > 0) h->nest--; }
-};
-
 // pass 1: (degree key, row id) pairs — the dense rows' degree is no criterion — and the degrees the sparse rows have
 template <typename I>
 __global__ __launch_bounds__(256) void k_go_degree_keys(const I *__restrict__ deg, int64_t n, int64_t thr,

@@ -124,15 +124,6 @@ __global__ __launch_bounds__(HT) void k_heat_convert(const unsigned long long *_
     out[i] = (F)((float)(long long)cnt[i] / denom);
 }
 
-}  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-namespace {
-
 template <typename I, typename N>
 static int heat_typed(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void *row_ptr, const void *col,
                       const void *order_r, const void *order_c, int64_t b, int feature_bytes, void *out) {

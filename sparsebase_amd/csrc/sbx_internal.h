@@ -163,6 +163,19 @@ void sbx_prof_end(sbx_handle_t h);
 
 #define SBX_LAUNCH_CHECK(h) SBX_HIP(h, hipGetLastError())
 
+// an argument check of an entry point: the message carries the entry point's name
+#define SBX_REQUIRE(h, cond, msg)                                       \
+  do {                                                                  \
+    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
+  } while (0)
+
+// an entry point that calls other entry points: the arena is not rewound while one of these lives
+struct NestGuard {
+  sbx_handle_t h;
+  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
+  ~NestGuard() { h->nest--; }
+};
+
 // ---- arena -----------------------------------------------------------------
 int sbx_arena_begin(sbx_handle_t h);  // start of an API call: rewinds (and consolidates)
 int sbx_arena_alloc(sbx_handle_t h, size_t bytes, void **out);

@@ -262,11 +262,6 @@ __global__ __launch_bounds__(JT) void k_jac_max_degree(const N *__restrict__ rp,
 
 }  // namespace
 
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 // steps 2-4 of one pass (FIXUP: the positions still NaN, own position only)
 template <typename I, typename N, typename F, bool FIXUP>
 static int jaccard_pass(sbx_handle_t h, int64_t n, int64_t nnz, const N *rp, const I *col, F *out, unsigned char *code,

@@ -17,7 +17,8 @@
 //   4. the entries are grouped by row already: the row offsets are the scan of step 2, and only if some row is out of
 //      order (sbx_csr_rows_sorted) its inside is sorted, stably (sbx_sort_segments).
 // The writer is a formatter of sbx_text.hip's kind over ITEMS — per row one head (the '\n' of the row before), its vertex
-// weights, its entries, and one last '\n' — whose lengths are summed per workgroup, scanned, and written through LDS.
+// weights, its entries, and one last '\n': GrJob, a job of the emit back end (sbx_text_emit.h), which sums the lengths per
+// workgroup, scans them, and writes through LDS.
 #include "sbgr.h"
 #include "sbx_dec2bin.h"
 #include "sbx_device.h"
@@ -135,134 +136,80 @@ __global__ __launch_bounds__(MX_THREADS) void k_gr_tokens(const char *__restrict
   if (bad) atomicOr(status, bad);
 }
 
-// ---- the formatter
-enum : int { GV_NONE = TI_NONE, GV_SIGNED = TI_SIGNED, GV_UNSIGNED = TI_UNSIGNED, GV_RECORD = TI_RECORD };
-
+// ---- the formatter: a job of the emit back end (sbx_text_emit.h).  A row has 1 + nvw + (its entries) items: the head,
+// the vertex weights, the entries; behind the last row comes one item more (the last '\n').
+template <typename RP, typename CI>
 struct GrJob {
-  const void *rp, *col, *val, *vwgt;
-  const sbx_decrec *rec_val, *rec_vw;  // GV_RECORD: of entry e at [e - e0], of weight j of row r at [(r - rb) * ncon + j]
+  const RP *rp;
+  const CI *col;
+  const void *val, *vwgt;
+  const sbx_decrec *rec_val, *rec_vw;  // TI_RECORD: of entry e at [e - e0], of weight j of row r at [(r - rb) * ncon + j]
   int64_t rb, re, e0, items, base;
   int nvw, ncon, ew, vw, vkind, vb, precision;
+  // key(r) = the first item of row r; key(re) is that last item
+  __device__ __forceinline__ int64_t key(int64_t r) const { return ((int64_t)rp[r] - e0) + (r - rb) * (int64_t)(1 + nvw); }
+  __device__ __forceinline__ void locate(int64_t k, int64_t *row, int64_t *sub) const {
+    int64_t lo = rb, hi = re;  // the last row r in [rb, re] with key(r) <= k
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (key(mid) <= k) lo = mid;
+      else hi = mid - 1;
+    }
+    *row = lo;
+    *sub = k - key(lo);
+  }
+  __device__ __forceinline__ int value(const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel, char *dst) const {
+    return dst ? tx_item_value_emit(vkind, vb, precision, arr, rec, i, irel, dst)
+               : tx_item_value_length(vkind, vb, precision, arr, rec, i, irel);
+  }
+  __device__ __forceinline__ unsigned item(int64_t r, int64_t sub, char *dst) const {
+    int o = 0;
+    if (r == re) {  // behind the last row
+      if (dst) dst[0] = '\n';
+      return 1;
+    }
+    if (sub == 0) {  // the head: the row before ends; a vertex-weighted row without weights still gets the two blanks
+      if (r > rb) {
+        if (dst) dst[o] = '\n';
+        o++;
+      }
+      if (vw && nvw == 0) {
+        if (dst) dst[o] = ' ', dst[o + 1] = ' ';
+        o += 2;
+      }
+      return (unsigned)o;
+    }
+    if (sub <= nvw) {  // vertex weight sub - 1: "w ", and two blanks more behind the last one
+      o = value(vwgt, rec_vw, r * ncon + (sub - 1), (r - rb) * ncon + (sub - 1), dst);
+      const int blanks = sub == nvw ? 3 : 1;
+      if (dst)
+        for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
+      return (unsigned)(o + blanks);
+    }
+    const int64_t e = (int64_t)rp[r] + (sub - 1 - nvw);
+    const bool last = e + 1 == (int64_t)rp[r + 1];
+    const int64_t c = (int64_t)col[e] + base;
+    if (dst) dst[0] = ' ';
+    o = 1;
+    o += dst ? tx_emit_signed(c, dst + o) : tx_len_signed(c);
+    if (ew) {
+      if (dst) dst[o] = ' ';
+      o++;
+      o += value(val, rec_val, e, e - e0, dst ? dst + o : nullptr);
+    }
+    if (!last) {
+      const int blanks = ew ? 2 : 1;
+      if (dst)
+        for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
+      o += blanks;
+    }
+    return (unsigned)o;
+  }
 };
 constexpr int GR_ITEM_MAX = 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 2;  // the longest item: an entry with its value and two blanks
 static_assert(GR_ITEM_MAX <= TX_LINE_MAX && SBX_DEC_MAX_CHARS + 3 <= TX_LINE_MAX, "an item fits its LDS slot");
 
-// Item k of the job.  A row has 1 + nvw + (its entries) items: the head, the vertex weights, the entries; behind the last
-// row comes one item more (the last '\n').  key(r) = the first item of row r; key(re) is that last item.
-template <typename RP>
-__device__ __forceinline__ int64_t gr_key(const GrJob &j, int64_t r) {
-  return ((int64_t)((const RP *)j.rp)[r] - j.e0) + (r - j.rb) * (int64_t)(1 + j.nvw);
-}
-template <typename RP>
-__device__ __forceinline__ void gr_locate(const GrJob &j, int64_t k, int64_t *row, int64_t *sub) {
-  int64_t lo = j.rb, hi = j.re;  // the last row r in [rb, re] with key(r) <= k
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (gr_key<RP>(j, mid) <= k) lo = mid;
-    else hi = mid - 1;
-  }
-  *row = lo;
-  *sub = k - gr_key<RP>(j, lo);
-}
-
-__device__ __forceinline__ int gr_value_length(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel) {
-  return tx_item_value_length(j.vkind, j.vb, j.precision, arr, rec, i, irel);
-}
-__device__ __forceinline__ int gr_value_emit(const GrJob &j, const void *arr, const sbx_decrec *rec, int64_t i, int64_t irel,
-                                             char *dst) {
-  return tx_item_value_emit(j.vkind, j.vb, j.precision, arr, rec, i, irel, dst);
-}
-
-// the text of item (r, sub): its length; written at dst unless dst is null
-template <typename RP, typename CI>
-__device__ __forceinline__ unsigned gr_item(const GrJob &j, int64_t r, int64_t sub, char *dst) {
-  int o = 0;
-  if (r == j.re) {  // behind the last row
-    if (dst) dst[0] = '\n';
-    return 1;
-  }
-  if (sub == 0) {  // the head: the row before ends; a vertex-weighted row without weights still gets the two blanks
-    if (r > j.rb) {
-      if (dst) dst[o] = '\n';
-      o++;
-    }
-    if (j.vw && j.nvw == 0) {
-      if (dst) dst[o] = ' ', dst[o + 1] = ' ';
-      o += 2;
-    }
-    return (unsigned)o;
-  }
-  if (sub <= j.nvw) {  // vertex weight sub - 1: "w ", and two blanks more behind the last one
-    const int64_t irel = (r - j.rb) * j.ncon + (sub - 1), i = r * j.ncon + (sub - 1);
-    o = dst ? gr_value_emit(j, j.vwgt, j.rec_vw, i, irel, dst) : gr_value_length(j, j.vwgt, j.rec_vw, i, irel);
-    const int blanks = sub == j.nvw ? 3 : 1;
-    if (dst)
-      for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
-    return (unsigned)(o + blanks);
-  }
-  const int64_t e = (int64_t)((const RP *)j.rp)[r] + (sub - 1 - j.nvw);
-  const bool last = e + 1 == (int64_t)((const RP *)j.rp)[r + 1];
-  const int64_t c = (int64_t)((const CI *)j.col)[e] + j.base;
-  if (dst) dst[0] = ' ';
-  o = 1;
-  o += dst ? tx_emit_signed(c, dst + o) : tx_len_signed(c);
-  if (j.ew) {
-    if (dst) dst[o] = ' ';
-    o++;
-    o += dst ? gr_value_emit(j, j.val, j.rec_val, e, e - j.e0, dst + o) : gr_value_length(j, j.val, j.rec_val, e, e - j.e0);
-  }
-  if (!last) {
-    const int blanks = j.ew ? 2 : 1;
-    if (dst)
-      for (int b = 0; b < blanks; b++) dst[o + b] = ' ';
-    o += blanks;
-  }
-  return (unsigned)o;
-}
-
-template <typename RP, typename CI>
-__global__ __launch_bounds__(TX_THREADS) void k_gr_lengths(const GrJob j, int64_t *__restrict__ block_len) {
-  __shared__ unsigned s_red[TX_THREADS / 64 + 1];
-  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  unsigned len = 0;
-  if (k < j.items) {
-    int64_t r, sub;
-    gr_locate<RP>(j, k, &r, &sub);
-    len = gr_item<RP, CI>(j, r, sub, nullptr);
-  }
-  const unsigned tot = sbx_block_sum<unsigned, TX_THREADS>(len, s_red);
-  if (threadIdx.x == 0) block_len[blockIdx.x] = (int64_t)tot;
-}
-
-template <typename RP, typename CI>
-__global__ __launch_bounds__(TX_THREADS) void k_gr_write(const GrJob j, const int64_t *__restrict__ block_off,
-                                                         char *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) char s_text[TX_LDS];
-  __shared__ unsigned s_scan[TX_THREADS / 64 + 1];
-  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  unsigned len = 0;
-  int64_t r = 0, sub = 0;
-  if (k < j.items) {
-    gr_locate<RP>(j, k, &r, &sub);
-    len = gr_item<RP, CI>(j, r, sub, nullptr);
-  }
-  unsigned total;
-  const unsigned off = sbx_block_exclusive_sum<unsigned, TX_THREADS>(len, s_scan, &total);
-  char *dst = out + block_off[blockIdx.x];
-  const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
-  if (len) gr_item<RP, CI>(j, r, sub, s_text + phase + off);
-  __syncthreads();
-  tx_block_store(s_text, phase, total, dst);
-}
-
 }  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-static unsigned gr_grid(int64_t count) { return (unsigned)((count + MX_THREADS - 1) / MX_THREADS); }
 
 extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, const void *text_dev, int64_t bytes,
                                 int64_t n, int64_t m, int fmt, int ncon, unsigned flags, int64_t capacity, void *row_out,
@@ -307,7 +254,7 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
   SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_tok));
   SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_ent));
   SBX_TRY(sbx_salloc(h, (size_t)lines + 1, &line_ncb));
-  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_lines, dim3(gr_grid((int64_t)lines + 1)), dim3(MX_THREADS), text,
+  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_lines, dim3(mx_grid((int64_t)lines + 1)), dim3(MX_THREADS), text,
               (const unsigned *)line_off, (int64_t)lines, (const unsigned *)tok_off, (int64_t)tokens, nvw,
               edge_weighted ? 1 : 0, line_tok, line_ent, line_ncb, status);
   SBX_LAUNCH_CHECK(h);
@@ -329,9 +276,9 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
   int32_t *rp = nullptr;
   SBX_TRY(sbx_salloc(h, (size_t)n_dim + 1, &rp));
   if (lines)
-    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_lines, dim3(gr_grid(lines)), dim3(MX_THREADS), (const unsigned *)line_ent,
+    SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_lines, dim3(mx_grid(lines)), dim3(MX_THREADS), (const unsigned *)line_ent,
                 (const unsigned *)line_ncb, (int64_t)lines, base, rp);
-  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_rest, dim3(gr_grid(n_dim + 1)), dim3(MX_THREADS), n_dim, base,
+  SBX_KLAUNCH(h, SBX_K_MTX, k_gr_row_ptr_rest, dim3(mx_grid(n_dim + 1)), dim3(MX_THREADS), n_dim, base,
               (int64_t)vertex_lines, (int32_t)nnz, rp);
   SBX_LAUNCH_CHECK(h);
   if (vwgt) SBX_HIP(h, hipMemsetAsync(vwgt, 0, (size_t)n_dim * (size_t)ncon * (size_t)vbytes, h->stream));
@@ -344,18 +291,13 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
     const uint64_t *pow5 = nullptr;
     const bool values = val || vwgt;
     if (values) SBX_TRY(sbx_pow5_table(h, &pow5));
-    const int vkind = !values ? 0 : (vt == SBX_V_F32 ? 2 : vt == SBX_V_F64 ? 3 : 1);
-    const int vsigned = (vt == SBX_V_I32 || vt == SBX_V_I64) ? 1 : 0;
+    const int vkind = mx_value_kind(vt, values), vsigned = mx_value_signed(vt);
 #define TOKENS(VK, VBX)                                                                                                  \
-  SBX_KLAUNCH(h, SBX_K_MTX, (k_gr_tokens<VK, VBX>), dim3(gr_grid(tokens)), dim3(MX_THREADS), text, bytes,                  \
+  SBX_KLAUNCH(h, SBX_K_MTX, (k_gr_tokens<VK, VBX>), dim3(mx_grid(tokens)), dim3(MX_THREADS), text, bytes,                  \
               (const unsigned *)tok_off, (int64_t)tokens, (const unsigned *)line_off, (int64_t)lines,                      \
               (const unsigned *)line_tok, (const unsigned *)line_ent, (const unsigned *)line_ncb, nvw, ncon,               \
               edge_weighted ? 1 : 0, zero_index ? 1 : 0, n_dim, nnz, vsigned, pow5, r32, c32, val, vwgt, status)
-    if (vkind == 0) TOKENS(0, 4);
-    else if (vkind == 1 && vbytes == 4) TOKENS(1, 4);
-    else if (vkind == 1) TOKENS(1, 8);
-    else if (vkind == 2) TOKENS(2, 4);
-    else TOKENS(3, 8);
+    MX_FOR_VALUE_KIND(vkind, vbytes, TOKENS);
 #undef TOKENS
     SBX_LAUNCH_CHECK(h);
     SBX_PROF_BYTES(h, SBX_K_MTX, bytes + nnz * (int64_t)(8 + (val ? vbytes : 0)));
@@ -402,19 +344,19 @@ extern "C" int sbgr_metis_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
 }
 
 template <typename RP, typename CI>
-static int gr_format_typed(sbx_handle_t h, GrJob job, void *text_out, int64_t capacity, int64_t *bytes_host) {
+static int gr_format_typed(sbx_handle_t h, GrJob<RP, CI> job, void *text_out, int64_t capacity, int64_t *bytes_host) {
   // the ends of the range, and that the offsets between them ascend (the item search relies on it)
   const int64_t rows = job.re - job.rb;
   int64_t hends[2] = {0, 0};
   bool hdesc = false;
-  SBX_TRY(tx_range_ends<RP>(h, (const RP *)job.rp, job.rb, job.re, hends, &hdesc));
+  SBX_TRY(tx_range_ends<RP>(h, job.rp, job.rb, job.re, hends, &hdesc));
   if (hdesc) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: row_ptr descends inside the row range");
   const int64_t entries = hends[1] - hends[0];
   job.e0 = hends[0];
   job.items = entries + rows * (int64_t)(1 + job.nvw) + 1;
   if (job.items >= ((int64_t)1 << 32))
     SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbgr_metis_format: 2^32 items and more in one call (pass the rows in sub-ranges)");
-  if (job.vkind == GV_RECORD) {
+  if (job.vkind == TI_RECORD) {
     sbx_decrec *rec = nullptr;
     if (job.ew && entries) {
       SBX_TRY(tx_records(h, (const char *)job.val + hends[0] * job.vb, nullptr, entries, job.vb, job.precision, &rec));
@@ -426,25 +368,7 @@ static int gr_format_typed(sbx_handle_t h, GrJob job, void *text_out, int64_t ca
       job.rec_vw = rec;
     }
   }
-  const unsigned grid = tx_grid(job.items);
-  int64_t *block_len = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &block_len));
-  SBX_HIP(h, hipMemsetAsync(block_len + grid, 0, sizeof(int64_t), h->stream));
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, (k_gr_lengths<RP, CI>), dim3(grid), dim3(TX_THREADS), job, block_len);
-  SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sbx_exclusive_scan_i64(h, block_len, block_len, (int64_t)grid + 1, nullptr));
-  int64_t total = 0;
-  SBX_TRY(sbx_readback(h, &total, block_len + grid, sizeof(int64_t)));
-  *bytes_host = total;
-  if (!text_out) return SBX_OK;  // the sizing call
-  if (capacity < total)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbgr_metis_format: the text has %lld bytes, text_out holds %lld", (long long)total,
-             (long long)capacity);
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, (k_gr_write<RP, CI>), dim3(grid), dim3(TX_THREADS), job, (const int64_t *)block_len,
-              (char *)text_out);
-  SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, entries * (int64_t)(sizeof(CI) + job.vb) + total);
-  return SBX_OK;
+  return tx_emit(h, "sbgr_metis_format", job, entries * (int64_t)(sizeof(CI) + job.vb), text_out, capacity, bytes_host);
 }
 
 extern "C" int sbgr_metis_format(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t row_begin, int64_t row_end,
@@ -468,22 +392,29 @@ extern "C" int sbgr_metis_format(sbx_handle_t h, sbx_index_type it, sbx_value_ty
   if (row_end == row_begin) return SBX_OK;
   SBX_REQUIRE(h, row_ptr, "row_ptr is needed");
   NestGuard guard(h);
-  GrJob job = {};
-  job.rp = row_ptr;
-  job.col = col;
-  job.val = val;
-  job.vwgt = vwgt;
-  job.rb = row_begin;
-  job.re = row_end;
-  job.base = index_base;
-  job.ncon = ncon;
-  job.nvw = vw ? ncon : 0;
-  job.ew = ew ? 1 : 0;
-  job.vw = vw ? 1 : 0;
-  job.vb = vbytes;
-  job.precision = precision;
-  job.vkind = tx_item_kind(vt);
-  if (it == SBX_I64) return gr_format_typed<int64_t, int64_t>(h, job, text_out, capacity, bytes_host);
-  if (it == SBX_I32_N64) return gr_format_typed<int64_t, int32_t>(h, job, text_out, capacity, bytes_host);
-  return gr_format_typed<int32_t, int32_t>(h, job, text_out, capacity, bytes_host);
+#define GR_JOB(RP, CI)                 \
+  GrJob<RP, CI> job = {};              \
+  job.rp = (const RP *)row_ptr;        \
+  job.col = (const CI *)col;           \
+  job.val = val;                       \
+  job.vwgt = vwgt;                     \
+  job.rb = row_begin;                  \
+  job.re = row_end;                    \
+  job.base = index_base;               \
+  job.ncon = ncon;                     \
+  job.nvw = vw ? ncon : 0;             \
+  job.ew = ew ? 1 : 0;                 \
+  job.vw = vw ? 1 : 0;                 \
+  job.vb = vbytes;                     \
+  job.precision = precision;           \
+  job.vkind = tx_item_kind(vt);        \
+  return gr_format_typed<RP, CI>(h, job, text_out, capacity, bytes_host)
+  if (it == SBX_I64) {
+    GR_JOB(int64_t, int64_t);
+  }
+  if (it == SBX_I32_N64) {
+    GR_JOB(int64_t, int32_t);
+  }
+  GR_JOB(int32_t, int32_t);
+#undef GR_JOB
 }

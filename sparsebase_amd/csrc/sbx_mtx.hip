@@ -12,7 +12,8 @@
 // caller's next step (sbx_coo_sort).  Tokens the stream extraction would choke on (hex,
 // inf/nan, garbage, a '.' in an integer field) are reported as an error instead of
 // reproducing the stream's fail state; values with more than 38 significant digits and a
-// non-zero tail are refused (SBX_ERR_UNSUPPORTED).
+// non-zero tail are refused (SBX_ERR_UNSUPPORTED).  The launch grid, the value kind of a value
+// type and the choice among the kernels' <VKIND, VB> instantiations are sbx_mtx_tokens.h's.
 #include "sbx_dec2bin.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
@@ -187,11 +188,6 @@ __global__ __launch_bounds__(MX_THREADS) void k_edge_compact(const int32_t *__re
 
 }  // namespace
 
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 // tables for the decimal conversion, built on first use (62 KB per handle)
 static int mx_pow5(sbx_handle_t h, const uint64_t **out) {
   if (!h->pow5) {
@@ -271,18 +267,13 @@ extern "C" int sbx_mtx_parse_coordinate(sbx_handle_t h, sbx_index_type it, sbx_v
     SBX_TRY(sbx_salloc(h, (size_t)entries + 1, &mirror));
     SBX_HIP(h, hipMemsetAsync(mirror + entries, 0, sizeof(unsigned), h->stream));
   }
-  const int vkind = vb == 0 ? 0 : (vt == SBX_V_F32 ? 2 : vt == SBX_V_F64 ? 3 : 1);
-  const int vsigned = (vt == SBX_V_I32 || vt == SBX_V_I64) ? 1 : 0;
-  const unsigned grid = (unsigned)((entries + MX_THREADS - 1) / MX_THREADS);
+  const int vkind = mx_value_kind(vt, vb != 0), vsigned = mx_value_signed(vt);
+  const unsigned grid = mx_grid(entries);
 #define PARSE(VK, VBX)                                                                                              \
   SBX_KLAUNCH(h, SBX_K_MTX, (k_mtx_parse<VK, VBX>), dim3(grid), dim3(MX_THREADS), text, bytes,                      \
               (const unsigned *)tok_off, entries, fields, symmetry, zero_index ? 1 : 0, upper ? 1 : 0, n_rows, n_cols, \
               vsigned, pow5, r0, c0, v0, mirror, status)
-  if (vkind == 0) PARSE(0, 4);
-  else if (vkind == 1 && vb == 4) PARSE(1, 4);
-  else if (vkind == 1) PARSE(1, 8);
-  else if (vkind == 2) PARSE(2, 4);
-  else PARSE(3, 8);
+  MX_FOR_VALUE_KIND(vkind, vb, PARSE);
 #undef PARSE
   SBX_LAUNCH_CHECK(h);
   int64_t nnz = entries;
@@ -297,11 +288,7 @@ extern "C" int sbx_mtx_parse_coordinate(sbx_handle_t h, sbx_index_type it, sbx_v
   SBX_KLAUNCH(h, SBX_K_MTX, (k_mtx_expand<VK, VBX>), dim3(grid), dim3(MX_THREADS), (const int32_t *)r0,           \
               (const int32_t *)c0, (const char *)v0, (const unsigned *)before, (const unsigned *)mirror, entries,   \
               symmetry == 2 ? 1 : 0, vsigned, (int32_t *)row_out, (int32_t *)col_out, (char *)val_out)
-    if (vkind == 0) EXPAND(0, 4);
-    else if (vkind == 1 && vb == 4) EXPAND(1, 4);
-    else if (vkind == 1) EXPAND(1, 8);
-    else if (vkind == 2) EXPAND(2, 4);
-    else EXPAND(3, 8);
+    MX_FOR_VALUE_KIND(vkind, vb, EXPAND);
 #undef EXPAND
     SBX_LAUNCH_CHECK(h);
   }
@@ -378,7 +365,7 @@ extern "C" int sbx_edge_list_parse(sbx_handle_t h, sbx_index_type it, sbx_value_
   SBX_TRY(sbx_salloc(h, 1, &dims));
   SBX_HIP(h, hipMemsetAsync(dims, 0, sizeof(EdgeDims), h->stream));
   SBX_HIP(h, hipMemsetAsync(outputs + entries, 0, sizeof(unsigned), h->stream));
-  const unsigned grid = (unsigned)((entries + MX_THREADS - 1) / MX_THREADS);
+  const unsigned grid = mx_grid(entries);
   SBX_KLAUNCH(h, SBX_K_MTX, k_edge_flags, dim3(grid), dim3(MX_THREADS), (const int32_t *)u, (const int32_t *)v, entries,
               remove_self ? 1 : 0, undirected ? 1 : 0, outputs, dims);
   SBX_TRY(sbx_exclusive_scan_u32(h, outputs, before, entries + 1, nullptr));
@@ -414,7 +401,7 @@ extern "C" int sbx_edge_list_parse(sbx_handle_t h, sbx_index_type it, sbx_value_
     SBX_TRY(sbx_salloc(h, (size_t)count + 1, &first));
     SBX_TRY(sbx_salloc(h, (size_t)count + 1, &fbefore));
     SBX_HIP(h, hipMemsetAsync(first + count, 0, sizeof(unsigned), h->stream));
-    const unsigned g2 = (unsigned)((count + MX_THREADS - 1) / MX_THREADS);
+    const unsigned g2 = mx_grid(count);
     SBX_KLAUNCH(h, SBX_K_MTX, k_edge_first, dim3(g2), dim3(MX_THREADS), (const int32_t *)r1, (const int32_t *)c1,
                 (int64_t)count, first);
     SBX_TRY(sbx_exclusive_scan_u32(h, first, fbefore, (int64_t)count + 1, nullptr));

@@ -1,7 +1,8 @@
 // sbx_mtx_tokens.h — the tokenizer of the text parsers: whitespace-separated tokens of a device text buffer, their
 // starts counted per tile and compacted in file order (count, scan, write).  Shared by the coordinate / edge-list
 // parsers (sbx_mtx.hip), the array-format parser (sbx_dense.hip) and the METIS graph and PaToH parsers (sbx_metis.hip,
-// sbx_patoh.hip), with the conversion of a value token that the first three share.
+// sbx_patoh.hip), with the conversion of a value token, the launch grid (mx_grid) and the dispatch over the kernels'
+// <VKIND, VB> instantiations (mx_value_kind, MX_FOR_VALUE_KIND).
 #pragma once
 #include "sbx_dec2bin.h"
 #include "sbx_device.h"
@@ -102,11 +103,21 @@ __device__ __forceinline__ uint64_t mx_parse_value(const char *__restrict__ s, i
   return sbx_decimal_to_double_bits(d, pow5) | ((uint64_t)d.neg << 63);
 }
 
-// an entry point that calls other entry points: the arena is not rewound while one of these lives
-struct NestGuard {
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
-  ~NestGuard() { h->nest--; }
-};
+static inline unsigned mx_grid(int64_t count) { return (unsigned)((count + MX_THREADS - 1) / MX_THREADS); }
+
+// The parsers' kernels are instantiated per <VKIND, VB>.  mx_value_kind: the VKIND of a value type (0 where no values are
+// read); MX_FOR_VALUE_KIND: CALL(VKIND, VB) for the one of the five instantiations that (vkind, vbytes) names.
+static inline int mx_value_kind(sbx_value_type vt, bool has_values) {
+  return !has_values ? 0 : vt == SBX_V_F32 ? 2 : vt == SBX_V_F64 ? 3 : 1;
+}
+static inline int mx_value_signed(sbx_value_type vt) { return (vt == SBX_V_I32 || vt == SBX_V_I64) ? 1 : 0; }
+#define MX_FOR_VALUE_KIND(vkind, vbytes, CALL)          \
+  do {                                                  \
+    if ((vkind) == 0) CALL(0, 4);                       \
+    else if ((vkind) == 1 && (vbytes) == 4) CALL(1, 4); \
+    else if ((vkind) == 1) CALL(1, 8);                  \
+    else if ((vkind) == 2) CALL(2, 4);                  \
+    else CALL(3, 8);                                    \
+  } while (0)
 
 }  // namespace

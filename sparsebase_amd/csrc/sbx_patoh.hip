@@ -17,7 +17,8 @@
 // before the sort; nets come out ascending because positions do and the sort is stable, and the offsets are a lower
 // bound of every cell in the sorted keys.  Nothing is read back between the steps and no row is sorted afterwards.
 // The writers are formatters of sbx_text.hip's kind over ITEMS — per net one head (its weight, or nothing) and its pins,
-// the '\n' riding on the net's last item — whose lengths are summed per workgroup, scanned, and written through LDS.
+// the '\n' riding on the net's last item: HgNetJob and HgWeightJob, jobs of the emit back end (sbx_text_emit.h), which sums
+// the lengths per workgroup, scans them, and writes through LDS.
 #include "sbhg.h"
 #include "sbx_countsort.h"
 #include "sbx_dec2bin.h"
@@ -224,7 +225,7 @@ static int hg_transpose(sbx_handle_t h, int64_t cells, int64_t nets, int64_t pin
   return SBX_OK;
 }
 
-// ---- the formatters: a job gives item k its place (locate) and its text (item: the length; written at dst unless null)
+// ---- the formatters' jobs (tx_emit, sbx_text_emit.h)
 template <typename XP, typename CI>
 struct HgNetJob {
   const XP *xpin;
@@ -288,74 +289,7 @@ struct HgWeightJob {
 };
 static_assert(1 + SBX_DEC_MAX_CHARS + 1 <= TX_LINE_MAX && 1 + 20 + 1 <= TX_LINE_MAX, "an item fits its LDS slot");
 
-template <typename Job>
-__global__ __launch_bounds__(TX_THREADS) void k_hg_lengths(const Job j, int64_t *__restrict__ block_len) {
-  __shared__ unsigned s_red[TX_THREADS / 64 + 1];
-  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  unsigned len = 0;
-  if (k < j.items) {
-    int64_t r, sub;
-    j.locate(k, &r, &sub);
-    len = j.item(r, sub, nullptr);
-  }
-  const unsigned tot = sbx_block_sum<unsigned, TX_THREADS>(len, s_red);
-  if (threadIdx.x == 0) block_len[blockIdx.x] = (int64_t)tot;
-}
-
-template <typename Job>
-__global__ __launch_bounds__(TX_THREADS) void k_hg_write(const Job j, const int64_t *__restrict__ block_off,
-                                                         char *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) char s_text[TX_LDS];
-  __shared__ unsigned s_scan[TX_THREADS / 64 + 1];
-  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  unsigned len = 0;
-  int64_t r = 0, sub = 0;
-  if (k < j.items) {
-    j.locate(k, &r, &sub);
-    len = j.item(r, sub, nullptr);
-  }
-  unsigned total;
-  const unsigned off = sbx_block_exclusive_sum<unsigned, TX_THREADS>(len, s_scan, &total);
-  char *dst = out + block_off[blockIdx.x];
-  const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
-  if (len) j.item(r, sub, s_text + phase + off);
-  __syncthreads();
-  tx_block_store(s_text, phase, total, dst);
-}
-
-// lengths, scan, the sizing call's answer, the write (steps 3 and 4 of a formatter); job.items >= 1
-template <typename Job>
-static int hg_emit(sbx_handle_t h, const char *who, const Job &job, void *text_out, int64_t capacity, int64_t *bytes_host) {
-  const unsigned grid = tx_grid(job.items);
-  int64_t *block_len = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &block_len));
-  SBX_HIP(h, hipMemsetAsync(block_len + grid, 0, sizeof(int64_t), h->stream));
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_hg_lengths<Job>, dim3(grid), dim3(TX_THREADS), job, block_len);
-  SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sbx_exclusive_scan_i64(h, block_len, block_len, (int64_t)grid + 1, nullptr));
-  int64_t total = 0;
-  SBX_TRY(sbx_readback(h, &total, block_len + grid, sizeof(int64_t)));
-  *bytes_host = total;
-  if (!text_out) return SBX_OK;  // the sizing call
-  if (capacity < total)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: the text has %lld bytes, text_out holds %lld", who, (long long)total,
-             (long long)capacity);
-  if (total == 0) return SBX_OK;
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_hg_write<Job>, dim3(grid), dim3(TX_THREADS), job, (const int64_t *)block_len,
-              (char *)text_out);
-  SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, job.items * (int64_t)4 + total);
-  return SBX_OK;
-}
-
 }  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-static unsigned mx_grid(int64_t count) { return (unsigned)((count + MX_THREADS - 1) / MX_THREADS); }
 
 static int hg_check_counts(sbx_handle_t h, const char *who, int64_t cells, int64_t nets, int64_t pins) {
   const int64_t lim = ((int64_t)1 << 31) - 1;
@@ -444,19 +378,14 @@ extern "C" int sbhg_patoh_parse(sbx_handle_t h, sbx_index_type it, sbx_value_typ
   int32_t *p32 = (int32_t *)pin_out;
   if (wide_ids && pins) SBX_TRY(sbx_salloc(h, (size_t)pins, &p32));
   if (tokens) {
-    const int vkind = !vbytes ? 0 : (vt == SBX_V_F32 ? 2 : vt == SBX_V_F64 ? 3 : 1);
-    const int vsigned = (vt == SBX_V_I32 || vt == SBX_V_I64) ? 1 : 0;
+    const int vkind = mx_value_kind(vt, vbytes != 0), vsigned = mx_value_signed(vt);
 #define TOKENS(VK, VBX)                                                                                                  \
   SBX_KLAUNCH(h, SBX_K_MTX, (k_hg_tokens<VK, VBX>), dim3(mx_grid(tokens)), dim3(MX_THREADS), text, bytes,                  \
               (const unsigned *)tok_off, (int64_t)tokens, (const unsigned *)line_off, (int64_t)lines,                      \
               (const unsigned *)line_tok, (const unsigned *)line_ent, (const unsigned *)line_ncb,                          \
               (const unsigned *)(status + 1), nets_weighted ? 1 : 0, base, cells, nets, pins, vsigned, p32, nwgt, cwgt,    \
               status)
-    if (vkind == 0) TOKENS(0, 4);
-    else if (vkind == 1 && vbytes == 4) TOKENS(1, 4);
-    else if (vkind == 1) TOKENS(1, 8);
-    else if (vkind == 2) TOKENS(2, 4);
-    else TOKENS(3, 8);
+    MX_FOR_VALUE_KIND(vkind, vbytes, TOKENS);
 #undef TOKENS
     SBX_LAUNCH_CHECK(h);
     SBX_PROF_BYTES(h, SBX_K_MTX, bytes + pins * (int64_t)4);
@@ -548,7 +477,7 @@ static int hg_format_typed(sbx_handle_t h, HgNetJob<XP, CI> job, void *text_out,
     SBX_TRY(tx_records(h, (const char *)job.wgt + job.rb * (int64_t)job.vb, nullptr, rows, job.vb, job.precision, &rec));
     job.rec = rec;
   }
-  return hg_emit(h, "sbhg_patoh_format", job, text_out, capacity, bytes_host);
+  return tx_emit(h, "sbhg_patoh_format", job, job.items * (int64_t)4, text_out, capacity, bytes_host);
 }
 
 extern "C" int sbhg_patoh_format(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t net_begin, int64_t net_end,
@@ -620,5 +549,5 @@ extern "C" int sbhg_patoh_format_weights(sbx_handle_t h, sbx_value_type vt, int6
     SBX_TRY(tx_records(h, (const char *)wgt + begin * (int64_t)vbytes, nullptr, job.items, vbytes, precision, &rec));
     job.rec = rec;
   }
-  return hg_emit(h, "sbhg_patoh_format_weights", job, text_out, capacity, bytes_host);
+  return tx_emit(h, "sbhg_patoh_format_weights", job, job.items * (int64_t)4, text_out, capacity, bytes_host);
 }

@@ -3025,11 +3025,6 @@ int classify_and_scan(sbx_handle_t h, const int2 *rec, I *rpo, I *sp, int64_t nr
 
 }  // namespace
 
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 extern "C" int sbx_inverse_permutation(sbx_handle_t h, sbx_index_type it, int64_t n, const void *perm,
                                        void *inv_out) {
   if (!h) return SBX_ERR_BAD_ARG;

@@ -166,12 +166,6 @@ __global__ __launch_bounds__(256) void k_range_nnz(const I *__restrict__ rp, con
   if (threadIdx.x == 0 && acc) atomicAdd(out, acc);
 }
 
-struct NestGuard {  // the nested entry points must not rewind the caller's scratch
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h_) : h(h_) { h->nest++; }
-  ~NestGuard() { if (h->nest > 0) h->nest--; }
-};
-
 int resolve_splits(sbx_handle_t h, sbx_comm_t comm, int64_t n, const int64_t *row_splits, Splits *sp, int64_t *chunk) {
   const int world = comm->world;
   if (world < 1 || world > MAX_WORLD) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "world size %d (supported: 1..%d)", world, MAX_WORLD);

@@ -641,15 +641,6 @@ __global__ __launch_bounds__(ST) void k_sb_out(const uint32_t *__restrict__ pos,
   SB_GRID_LOOP(i, n) out[i] = (I)pos[i];
 }
 
-}  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-namespace {
-
 struct SbCall {
   sbx_handle_t h;
   int64_t n, k;

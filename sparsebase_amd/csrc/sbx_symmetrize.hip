@@ -26,11 +26,6 @@
 #define SBSYM_FASTPATH 1  // 0: the keep pass searches whatever the comparison found (the A/B of tools/symmetrize_probe.py)
 #endif
 
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 namespace {
 
 constexpr int SY = 256;  // threads per workgroup; every kernel is a grid-stride loop of one item (four in k_sym_equal)

@@ -11,120 +11,84 @@
 //                        128-bit fast path; the few values it does not reach are appended to a list
 //   2. k_text_long       the listed values through the multi-limb path (per-thread limb arrays: scratch memory, which
 //                        is why it is a kernel of its own and not a branch of the kernel every value goes through)
-//   3. k_text_lengths    the length of every line, summed per workgroup; a 64-bit scan of the sums gives every
+//   3. k_tx_lengths      the length of every line, summed per workgroup; a 64-bit scan of the sums gives every
 //                        workgroup's offset in the text and the total, which is read back (the sizing call ends here)
-//   4. k_text_write      the lengths again, scanned inside the workgroup; every thread writes its line into LDS at its
+//   4. k_tx_write        the lengths again, scanned inside the workgroup; every thread writes its line into LDS at its
 //                        offset, and the workgroup's span goes to global memory in aligned 16-byte words — the LDS image
 //                        is shifted by the span's misalignment so that LDS words and global words coincide — with at
 //                        most 15 single bytes at either end.  Nothing at or beyond the text's length is touched.
+// Steps 3 and 4 are the emit back end of sbx_text_emit.h (tx_emit) over a TextJob, whose items are the lines.
 // The conversion runs once (the records are kept between 3 and 4); the digits of the indices are produced twice.
 #include "sbx_bin2dec.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
 #include "sbx_text.h"
-#include "sbx_text_emit.h"  // integer printing, decimal records, the LDS write-out: shared with sbx_metis.hip
+#include "sbx_text_emit.h"  // integer and value printing, decimal records, the emit back end: shared with sbx_metis.hip, sbx_patoh.hip
 
 namespace {
-
-enum : int { TV_NONE = 0, TV_SIGNED, TV_UNSIGNED, TV_RECORD, TV_ZERO };
 
 struct TextJob {
   const void *row, *col, *val;
   const int32_t *slot;    // dense: the entry stored in cell i, -1 where none is
-  const sbx_decrec *rec;  // TV_RECORD: one per line
-  int64_t count, base;
+  const sbx_decrec *rec;  // TI_RECORD: one per line
+  int64_t items, base;
   int idx64, coords, vkind, vb, precision;
   unsigned flags;
+  __device__ __forceinline__ int64_t id(const void *a, int64_t i) const {
+    return idx64 ? ((const int64_t *)a)[i] : (int64_t)((const int32_t *)a)[i];
+  }
+  __device__ __forceinline__ bool keep(int64_t r, int64_t c) const {
+    if ((flags & SBX_TEXT_LOWER) && c > r) return false;
+    if ((flags & SBX_TEXT_NO_DIAGONAL) && c == r) return false;
+    return true;
+  }
+  __device__ __forceinline__ void locate(int64_t k, int64_t *line, int64_t *sub) const {
+    *line = k;
+    *sub = 0;
+  }
+  // the value of line i: a record as it is (an empty dense cell's is +0 already); "0" for the zero kind and for a dense
+  // cell that holds nothing
+  __device__ __forceinline__ int value_length(int64_t i) const {
+    if (vkind == TI_RECORD) return tx_item_value_length(TI_RECORD, vb, precision, val, rec, i, i);
+    int64_t src = i;
+    if (vkind == TI_ZERO || (slot && (src = slot[i]) < 0)) return 1;
+    return tx_item_value_length(vkind, vb, precision, val, rec, src, i);
+  }
+  __device__ __forceinline__ int value_emit(int64_t i, char *dst) const {
+    if (vkind == TI_RECORD) return tx_item_value_emit(TI_RECORD, vb, precision, val, rec, i, i, dst);
+    int64_t src = i;
+    if (vkind == TI_ZERO || (slot && (src = slot[i]) < 0)) {
+      dst[0] = '0';
+      return 1;
+    }
+    return tx_item_value_emit(vkind, vb, precision, val, rec, src, i, dst);
+  }
+  // line i with its '\n'; 0 for an entry that is not kept.  One decision on dst: the length pass carries no stores and
+  // the write pass no tests
+  __device__ __forceinline__ unsigned item(int64_t i, int64_t, char *dst) const {
+    return dst ? line<true>(i, dst) : line<false>(i, nullptr);
+  }
+  template <bool EMIT>
+  __device__ __forceinline__ unsigned line(int64_t i, char *dst) const {
+    int o = 0;
+    if (coords) {
+      const int64_t r = id(row, i), c = id(col, i);
+      if (!keep(r, c)) return 0;
+      o = EMIT ? tx_emit_signed(r + base, dst) : tx_len_signed(r + base);
+      if (EMIT) dst[o] = ' ';
+      o++;
+      o += EMIT ? tx_emit_signed(c + base, dst + o) : tx_len_signed(c + base);
+      if (vkind != TI_NONE) {
+        if (EMIT) dst[o] = ' ';
+        o++;
+      }
+    }
+    if (vkind != TI_NONE) o += EMIT ? value_emit(i, dst + o) : value_length(i);
+    if (EMIT) dst[o] = '\n';
+    return (unsigned)(o + 1);
+  }
 };
-
-__device__ __forceinline__ int64_t tx_id(const void *a, int idx64, int64_t i) {
-  return idx64 ? ((const int64_t *)a)[i] : (int64_t)((const int32_t *)a)[i];
-}
-__device__ __forceinline__ bool tx_keep(unsigned flags, int64_t r, int64_t c) {
-  if ((flags & SBX_TEXT_LOWER) && c > r) return false;
-  if ((flags & SBX_TEXT_NO_DIAGONAL) && c == r) return false;
-  return true;
-}
-// the integer value of line i: false where the dense cell holds nothing
-__device__ __forceinline__ bool tx_source(const TextJob &j, int64_t i, int64_t *src) {
-  *src = i;
-  if (j.slot) {
-    const int32_t s = j.slot[i];
-    if (s < 0) return false;
-    *src = s;
-  }
-  return true;
-}
-
-__device__ __forceinline__ int tx_value_length(const TextJob &j, int64_t i) {
-  if (j.vkind == TV_RECORD) return sbx_b2d::text_length(j.rec[i], j.precision);
-  int64_t src;
-  if (j.vkind == TV_ZERO || !tx_source(j, i, &src)) return 1;
-  if (j.vkind == TV_SIGNED)
-    return tx_len_signed(j.vb == 4 ? (int64_t)((const int32_t *)j.val)[src] : ((const int64_t *)j.val)[src]);
-  return sbx_b2d::length_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)j.val)[src] : ((const uint64_t *)j.val)[src]);
-}
-
-__device__ __forceinline__ int tx_value_emit(const TextJob &j, int64_t i, char *dst) {
-  if (j.vkind == TV_RECORD) return sbx_b2d::emit(j.rec[i], j.precision, dst);
-  int64_t src;
-  if (j.vkind == TV_ZERO || !tx_source(j, i, &src)) {
-    dst[0] = '0';
-    return 1;
-  }
-  if (j.vkind == TV_SIGNED)
-    return tx_emit_signed(j.vb == 4 ? (int64_t)((const int32_t *)j.val)[src] : ((const int64_t *)j.val)[src], dst);
-  return sbx_b2d::emit_u64(j.vb == 4 ? (uint64_t)((const uint32_t *)j.val)[src] : ((const uint64_t *)j.val)[src], dst);
-}
-
-// length of line i with its '\n', 0 for an entry that is not kept
-__device__ __forceinline__ unsigned tx_line_length(const TextJob &j, int64_t i) {
-  if (i >= j.count) return 0;
-  unsigned len = 1;
-  if (j.coords) {
-    const int64_t r = tx_id(j.row, j.idx64, i), c = tx_id(j.col, j.idx64, i);
-    if (!tx_keep(j.flags, r, c)) return 0;
-    len += (unsigned)(tx_len_signed(r + j.base) + 1 + tx_len_signed(c + j.base));
-    if (j.vkind != TV_NONE) len += 1;
-  }
-  if (j.vkind != TV_NONE) len += (unsigned)tx_value_length(j, i);
-  return len;
-}
-
-__device__ __forceinline__ void tx_line_emit(const TextJob &j, int64_t i, char *dst) {
-  int o = 0;
-  if (j.coords) {
-    o += tx_emit_signed(tx_id(j.row, j.idx64, i) + j.base, dst);
-    dst[o++] = ' ';
-    o += tx_emit_signed(tx_id(j.col, j.idx64, i) + j.base, dst + o);
-    if (j.vkind != TV_NONE) dst[o++] = ' ';
-  }
-  if (j.vkind != TV_NONE) o += tx_value_emit(j, i, dst + o);
-  dst[o] = '\n';
-}
-
-// ---- 3 / 4: lengths, write-out
-__global__ __launch_bounds__(TX_THREADS) void k_text_lengths(const TextJob j, int64_t *__restrict__ block_len) {
-  __shared__ unsigned s_red[TX_THREADS / 64 + 1];
-  const int64_t i = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  const unsigned tot = sbx_block_sum<unsigned, TX_THREADS>(tx_line_length(j, i), s_red);
-  if (threadIdx.x == 0) block_len[blockIdx.x] = (int64_t)tot;
-}
-
-__global__ __launch_bounds__(TX_THREADS) void k_text_write(const TextJob j, const int64_t *__restrict__ block_off,
-                                                           char *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) char s_text[TX_LDS];
-  __shared__ unsigned s_scan[TX_THREADS / 64 + 1];
-  const int64_t i = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
-  const unsigned len = tx_line_length(j, i);
-  unsigned total;
-  const unsigned off = sbx_block_exclusive_sum<unsigned, TX_THREADS>(len, s_scan, &total);
-  char *dst = out + block_off[blockIdx.x];
-  const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
-  if (len) tx_line_emit(j, i, s_text + phase + off);
-  __syncthreads();
-  tx_block_store(s_text, phase, total, dst);
-}
+static_assert(20 + 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 1 <= TX_LINE_MAX, "a line fits its LDS slot");
 
 // ---- symmetry check
 struct SymCounts {
@@ -279,63 +243,23 @@ __global__ __launch_bounds__(TX_THREADS) void k_dense_slots(const I *__restrict_
   if (atomicCAS(&slot[c * n + r], -1, (int32_t)i) != -1) atomicOr(status, DN_DUPLICATE);
 }
 
-struct NestGuard {
-  sbx_handle_t h;
-  explicit NestGuard(sbx_handle_t h) : h(h) { h->nest++; }
-  ~NestGuard() { h->nest--; }
-};
-
 }  // namespace
-
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
-static int tx_value_kind(sbx_value_type vt) {
-  switch (vt) {
-    case SBX_V_NONE: return TV_NONE;
-    case SBX_V_I32: case SBX_V_I64: return TV_SIGNED;
-    case SBX_V_U32: case SBX_V_U64: return TV_UNSIGNED;
-    case SBX_V_F32: case SBX_V_F64: return TV_RECORD;
-  }
-  return -1;
-}
 
 // steps 1 to 4 for a job whose arrays are set; the caller has begun the arena and holds a NestGuard
 static int tx_format(sbx_handle_t h, const char *who, TextJob job, void *text_out, int64_t capacity, int64_t *bytes_host) {
   *bytes_host = 0;
-  const int64_t count = job.count;
-  if (count == 0) return SBX_OK;
-  if (count >= ((int64_t)1 << 32))
+  if (job.items == 0) return SBX_OK;
+  if (job.items >= ((int64_t)1 << 32))
     SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: 2^32 lines and more in one call (pass the entries in sub-ranges)", who);
-  const unsigned grid = tx_grid(count);
-  if (job.vkind == TV_RECORD) {
+  if (job.vkind == TI_RECORD) {
     sbx_decrec *rec = nullptr;
-    SBX_TRY(tx_records(h, job.val, job.slot, count, job.vb, job.precision, &rec));
+    SBX_TRY(tx_records(h, job.val, job.slot, job.items, job.vb, job.precision, &rec));
     job.rec = rec;
   }
   const int64_t line_in = (job.coords ? 2 * (job.idx64 ? 8 : 4) : 0) + (job.slot ? 4 : 0) +
-                          (job.vkind == TV_RECORD ? (int64_t)sizeof(sbx_decrec) : job.vkind == TV_NONE ? 0 : job.vb);
-  int64_t *block_len = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &block_len));
-  SBX_HIP(h, hipMemsetAsync(block_len + grid, 0, sizeof(int64_t), h->stream));
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_text_lengths, dim3(grid), dim3(TX_THREADS), job, block_len);
-  SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, count * line_in);
-  SBX_TRY(sbx_exclusive_scan_i64(h, block_len, block_len, (int64_t)grid + 1, nullptr));
-  int64_t total = 0;
-  SBX_TRY(sbx_readback(h, &total, block_len + grid, sizeof(int64_t)));
-  *bytes_host = total;
-  if (!text_out) return SBX_OK;  // the sizing call
-  if (capacity < total)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: the text has %lld bytes, text_out holds %lld", who, (long long)total, (long long)capacity);
-  if (total == 0) return SBX_OK;
-  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_text_write, dim3(grid), dim3(TX_THREADS), job, (const int64_t *)block_len,
-              (char *)text_out);
-  SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, count * line_in + total);
-  return SBX_OK;
+                          (job.vkind == TI_RECORD ? (int64_t)sizeof(sbx_decrec) : job.vkind == TI_NONE ? 0 : job.vb);
+  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, job.items * line_in);  // the lengths pass reads the lines too
+  return tx_emit(h, who, job, job.items * line_in, text_out, capacity, bytes_host);
 }
 
 extern "C" int sbx_text_format_values(sbx_handle_t h, sbx_value_type vt, int64_t count, const void *vals, int precision,
@@ -343,13 +267,13 @@ extern "C" int sbx_text_format_values(sbx_handle_t h, sbx_value_type vt, int64_t
   if (!h) return SBX_ERR_BAD_ARG;
   SBX_REQUIRE(h, bytes_host && count >= 0 && capacity >= 0 && (count == 0 || vals), "bad argument");
   SBX_REQUIRE(h, precision >= 1 && precision <= 17, "precision: 1..17");
-  const int vkind = tx_value_kind(vt);
-  SBX_REQUIRE(h, vkind > TV_NONE, "a value type is needed");
+  const int vkind = tx_item_kind(vt);
+  SBX_REQUIRE(h, vkind > TI_NONE, "a value type is needed");
   SBX_TRY(sbx_arena_begin(h));
   NestGuard guard(h);
   TextJob job = {};
   job.val = vals;
-  job.count = count;
+  job.items = count;
   job.vkind = vkind;
   job.vb = sbx_value_bytes(vt);
   job.precision = precision;
@@ -365,21 +289,21 @@ extern "C" int sbx_text_format_coordinate(sbx_handle_t h, sbx_index_type it, sbx
   SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64, "unknown index type");
   SBX_REQUIRE(h, precision >= 1 && precision <= 17, "precision: 1..17");
   SBX_REQUIRE(h, (flags & ~(SBX_TEXT_LOWER | SBX_TEXT_NO_DIAGONAL | SBX_TEXT_PATTERN)) == 0, "unknown flag");
-  int vkind = tx_value_kind(vt);
+  int vkind = tx_item_kind(vt);
   SBX_REQUIRE(h, vkind >= 0, "unknown value type");
-  if (!val || (flags & SBX_TEXT_PATTERN)) vkind = TV_NONE;
+  if (!val || (flags & SBX_TEXT_PATTERN)) vkind = TI_NONE;
   SBX_TRY(sbx_arena_begin(h));
   NestGuard guard(h);
   TextJob job = {};
   job.row = row;
   job.col = col;
   job.val = val;
-  job.count = nnz;
+  job.items = nnz;
   job.base = index_base;
   job.idx64 = it == SBX_I64 ? 1 : 0;
   job.coords = 1;
   job.vkind = vkind;
-  job.vb = vkind == TV_NONE ? 0 : sbx_value_bytes(vt);
+  job.vb = vkind == TI_NONE ? 0 : sbx_value_bytes(vt);
   job.precision = precision;
   job.flags = flags;
   return tx_format(h, __func__, job, text_out, capacity, bytes_host);
@@ -413,9 +337,9 @@ static int dense_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, 
   TextJob job = {};
   job.val = val;
   job.slot = slot;
-  job.count = cells;
-  job.vkind = (val && vt != SBX_V_NONE) ? tx_value_kind(vt) : TV_ZERO;
-  job.vb = job.vkind == TV_ZERO ? 0 : sbx_value_bytes(vt);
+  job.items = cells;
+  job.vkind = (val && vt != SBX_V_NONE) ? tx_item_kind(vt) : TI_ZERO;
+  job.vb = job.vkind == TI_ZERO ? 0 : sbx_value_bytes(vt);
   job.precision = precision;
   return tx_format(h, "sbx_text_format_dense", job, text_out, capacity, bytes_host);
 }
@@ -428,7 +352,7 @@ extern "C" int sbx_text_format_dense(sbx_handle_t h, sbx_index_type it, sbx_valu
   SBX_REQUIRE(h, bytes_host && n >= 0 && m >= 0 && nnz >= 0 && capacity >= 0 && (nnz == 0 || (row && col)), "bad argument");
   SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64, "unknown index type");
   SBX_REQUIRE(h, precision >= 1 && precision <= 17, "precision: 1..17");
-  SBX_REQUIRE(h, tx_value_kind(vt) >= 0, "unknown value type");
+  SBX_REQUIRE(h, tx_item_kind(vt) >= 0, "unknown value type");
   if ((n > 0 && m > 0 && n > (((int64_t)1 << 31) - 1) / m) || nnz >= ((int64_t)1 << 31))
     SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbx_text_format_dense: n * m (and nnz) must be below 2^31");
   SBX_TRY(sbx_arena_begin(h));
@@ -496,7 +420,7 @@ extern "C" int sbx_coo_symmetry_check(sbx_handle_t h, sbx_index_type it, sbx_val
   if (it == SBX_I32_N64) it = SBX_I32;  // (no offset array)
   SBX_REQUIRE(h, result_host && n >= 0 && nnz >= 0 && (nnz == 0 || (row && col)), "bad argument");
   SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64, "unknown index type");
-  SBX_REQUIRE(h, tx_value_kind(vt) >= 0, "unknown value type");
+  SBX_REQUIRE(h, tx_item_kind(vt) >= 0, "unknown value type");
   if (vt == SBX_V_NONE) val = nullptr;
   result_host[0] = 1;
   result_host[1] = result_host[2] = 0;
@@ -557,7 +481,7 @@ extern "C" int sbx_coo_undirected_unique(sbx_handle_t h, sbx_index_type it, sbx_
   if (it == SBX_I32_N64) it = SBX_I32;  // (no offset array)
   SBX_REQUIRE(h, nnz_host && nnz >= 0 && (nnz == 0 || (row && col)), "bad argument");
   SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64, "unknown index type");
-  SBX_REQUIRE(h, tx_value_kind(vt) >= 0, "unknown value type");
+  SBX_REQUIRE(h, tx_item_kind(vt) >= 0, "unknown value type");
   if (nnz >= ((int64_t)1 << 31)) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbx_coo_undirected_unique: nnz must be below 2^31");
   if (vt == SBX_V_NONE) val = nullptr;
   *nnz_host = 0;

@@ -1,6 +1,9 @@
-// sbx_text_emit.h — what the text formatters share: integer printing, floating-point values -> decimal records
-// (sbx_bin2dec.h) and the write-out of a workgroup's LDS text image in aligned 16-byte words.  Used by the Matrix Market /
-// edge-list formatters (sbx_text.hip), the METIS graph formatter (sbx_metis.hip) and the PaToH formatters (sbx_patoh.hip).
+// sbx_text_emit.h — what the text formatters share: integer and value printing, floating-point values -> decimal records
+// (sbx_bin2dec.h), and the emit back end, tx_emit<Job>: the lengths of a job's items summed per workgroup, scanned and
+// read back, then the items written through LDS, a workgroup's text image going out in aligned 16-byte words.  A formatter
+// is a job (items, locate, item) and what it does before tx_emit.  Used by the Matrix Market / edge-list formatters
+// (sbx_text.hip: TextJob), the METIS graph formatter (sbx_metis.hip: GrJob) and the PaToH formatters (sbx_patoh.hip:
+// HgNetJob, HgWeightJob).
 #pragma once
 #include "sbx_bin2dec.h"
 #include "sbx_device.h"
@@ -9,9 +12,9 @@
 namespace {  // (kernels in a header shared by several translation units: internal linkage)
 
 constexpr int TX_THREADS = 256;
-constexpr int TX_LINE_MAX = 68;  // 2 x 20 index characters, 2 blanks, SBX_DEC_MAX_CHARS, '\n', rounded up
+constexpr int TX_LINE_MAX = 68;  // the LDS slot of an item (every job asserts that its longest one fits): a coordinate line
+                                 // is 2 x 20 index characters, 2 blanks, SBX_DEC_MAX_CHARS, '\n', rounded up
 constexpr int TX_LDS = TX_THREADS * TX_LINE_MAX + 16;
-static_assert(20 + 1 + 20 + 1 + SBX_DEC_MAX_CHARS + 1 <= TX_LINE_MAX, "a line fits its LDS slot");
 
 __device__ __forceinline__ int tx_len_signed(int64_t v) {
   return v < 0 ? 1 + sbx_b2d::length_u64(0ull - (uint64_t)v) : sbx_b2d::length_u64((uint64_t)v);
@@ -25,12 +28,17 @@ __device__ __forceinline__ int tx_emit_signed(int64_t v, char *dst) {
 }
 
 // ---- a value of the formatters' items: how it is kept (vkind) and its text.  TI_RECORD: floating point, printed from the
-// decimal record rec[irel] (tx_records); the integer kinds print arr[i], a value of vb bytes, in full
-enum : int { TI_NONE = 0, TI_SIGNED, TI_UNSIGNED, TI_RECORD };
-static inline int tx_item_kind(sbx_value_type vt) {
-  return (vt == SBX_V_F32 || vt == SBX_V_F64) ? TI_RECORD
-         : (vt == SBX_V_I32 || vt == SBX_V_I64) ? TI_SIGNED
-         : vt == SBX_V_NONE ? TI_NONE : TI_UNSIGNED;
+// decimal record rec[irel] (tx_records); the integer kinds print arr[i], a value of vb bytes, in full.  TI_ZERO is the
+// array format's alone (sbx_text.hip): no value is kept, every cell prints "0"
+enum : int { TI_NONE = 0, TI_SIGNED, TI_UNSIGNED, TI_RECORD, TI_ZERO };
+static inline int tx_item_kind(sbx_value_type vt) {  // -1: no value type
+  switch (vt) {
+    case SBX_V_NONE: return TI_NONE;
+    case SBX_V_I32: case SBX_V_I64: return TI_SIGNED;
+    case SBX_V_U32: case SBX_V_U64: return TI_UNSIGNED;
+    case SBX_V_F32: case SBX_V_F64: return TI_RECORD;
+  }
+  return -1;
 }
 __device__ __forceinline__ int tx_item_value_length(int vkind, int vb, int precision, const void *arr, const sbx_decrec *rec,
                                                int64_t i, int64_t irel) {
@@ -167,6 +175,71 @@ static int tx_records(sbx_handle_t h, const void *val, const int32_t *slot, int6
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_TEXT_FORMAT, count * (int64_t)(vb + sizeof(sbx_decrec)));
   *rec_out = rec;
+  return SBX_OK;
+}
+
+// ---- the emit back end (steps 3 and 4 of a formatter).  A job gives item k of its `items` a place, locate(k, &row,
+// &sub), and a text, item(row, sub, dst): the length; written at dst unless dst is null.  An item of length 0 is left out.
+template <typename Job>
+__global__ __launch_bounds__(TX_THREADS) void k_tx_lengths(const Job j, int64_t *__restrict__ block_len) {
+  __shared__ unsigned s_red[TX_THREADS / 64 + 1];
+  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  unsigned len = 0;
+  if (k < j.items) {
+    int64_t r, sub;
+    j.locate(k, &r, &sub);
+    len = j.item(r, sub, nullptr);
+  }
+  const unsigned tot = sbx_block_sum<unsigned, TX_THREADS>(len, s_red);
+  if (threadIdx.x == 0) block_len[blockIdx.x] = (int64_t)tot;
+}
+
+template <typename Job>
+__global__ __launch_bounds__(TX_THREADS) void k_tx_write(const Job j, const int64_t *__restrict__ block_off,
+                                                         char *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) char s_text[TX_LDS];
+  __shared__ unsigned s_scan[TX_THREADS / 64 + 1];
+  const int64_t k = (int64_t)blockIdx.x * TX_THREADS + threadIdx.x;
+  unsigned len = 0;
+  int64_t r = 0, sub = 0;
+  if (k < j.items) {
+    j.locate(k, &r, &sub);
+    len = j.item(r, sub, nullptr);
+  }
+  unsigned total;
+  const unsigned off = sbx_block_exclusive_sum<unsigned, TX_THREADS>(len, s_scan, &total);
+  char *dst = out + block_off[blockIdx.x];
+  const unsigned phase = (unsigned)((uintptr_t)dst & 15u);  // the LDS image starts at the same offset inside a 16-byte word
+  if (len) j.item(r, sub, s_text + phase + off);
+  __syncthreads();
+  tx_block_store(s_text, phase, total, dst);
+}
+
+// The lengths summed per workgroup, a 64-bit scan of the sums (every workgroup's offset in the text, and the total, which
+// is read back: the sizing call ends here), the write.  job.items >= 1; in_bytes: what the job reads, for the profiler;
+// the caller has begun the arena and holds a NestGuard.
+template <typename Job>
+static int tx_emit(sbx_handle_t h, const char *who, const Job &job, int64_t in_bytes, void *text_out, int64_t capacity,
+                   int64_t *bytes_host) {
+  const unsigned grid = tx_grid(job.items);
+  int64_t *block_len = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)grid + 1, &block_len));
+  SBX_HIP(h, hipMemsetAsync(block_len + grid, 0, sizeof(int64_t), h->stream));
+  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_tx_lengths<Job>, dim3(grid), dim3(TX_THREADS), job, block_len);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(sbx_exclusive_scan_i64(h, block_len, block_len, (int64_t)grid + 1, nullptr));
+  int64_t total = 0;
+  SBX_TRY(sbx_readback(h, &total, block_len + grid, sizeof(int64_t)));
+  *bytes_host = total;
+  if (!text_out) return SBX_OK;  // the sizing call
+  if (capacity < total)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: the text has %lld bytes, text_out holds %lld", who, (long long)total,
+             (long long)capacity);
+  if (total == 0) return SBX_OK;
+  SBX_KLAUNCH(h, SBX_K_TEXT_WRITE, k_tx_write<Job>, dim3(grid), dim3(TX_THREADS), job, (const int64_t *)block_len,
+              (char *)text_out);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_TEXT_WRITE, in_bytes + total);
   return SBX_OK;
 }
 

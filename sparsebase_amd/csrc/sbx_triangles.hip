@@ -361,11 +361,6 @@ __global__ __launch_bounds__(TT) void k_tc_block(const uint64_t *__restrict__ it
 
 }  // namespace
 
-#define SBX_REQUIRE(h, cond, msg)                                       \
-  do {                                                                  \
-    if (!(cond)) SBX_FAIL(h, SBX_ERR_BAD_ARG, "%s: %s", __func__, msg); \
-  } while (0)
-
 static int tc_offsets(sbx_handle_t h, const uint64_t *keys, int64_t cnt_host, const uint32_t *cnt_dev, int64_t n,
                       uint32_t *off) {
   SBX_KLAUNCH(h, SBX_K_FEATURE, k_tc_offsets, dim3(sbx_grid_for(n + 1, TT, (int64_t)h->num_cus * 32)), dim3(TT), keys,

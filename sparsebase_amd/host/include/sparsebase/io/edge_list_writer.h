@@ -106,8 +106,7 @@ class EdgeListWriter {
         val = v2;
         nnz = left;
       }
-      std::ofstream out(filename_, std::ios::binary);
-      if (!out.is_open()) throw utils::WriterException("cannot open " + filename_ + " for writing");
+      std::ofstream out = detail::OpenText(filename_);
       detail::TextStreamer text(dev);
       const int precision = precision_;
       text.Stream(out, nnz, [&](int64_t b, int64_t c, void *o, int64_t cap, int64_t *bytes) {
@@ -115,8 +114,7 @@ class EdgeListWriter {
                                           val ? (const void *)((const char *)val + (size_t)b * vb) : nullptr, 0, precision, 0u, o,
                                           cap, bytes);
       });
-      out.close();
-      if (!out) throw utils::WriterException("writing " + filename_ + " failed");
+      detail::CloseText(out, filename_);
     } catch (...) {
       if (!scratch) {
         dev.Free(r2);

@@ -95,8 +95,7 @@ class MetisGraphWriter {
     }
     detail::WriterCheck(dev, sbx_coo_to_csr(dev.handle(), it, SBX_V_NONE, dim0, dim0, nnz, row, nullptr, nullptr, rp.get(), nullptr,
                                             nullptr, SBX_FLAG_MOVE | (rows_sorted ? SBX_FLAG_ROWS_SORTED : 0u)));
-    std::ofstream out(filename_, std::ios::binary);
-    if (!out.is_open()) throw utils::WriterException("cannot open " + filename_ + " for writing");
+    std::ofstream out = detail::OpenText(filename_);
     out << " " << (dim0 - row_begin) << " " << nnz / 2;  // metis_graph_writer.cc:41
     if (!is_void) {
       out << " " << (ew && !vw ? "1" : ew ? "11" : "10");  // :56-63
@@ -111,7 +110,8 @@ class MetisGraphWriter {
     // its entries + 1 + ncon items, and a chunk is the longest run of rows that weighs at most SBX_TEXT_CHUNK_ENTRIES,
     // one row at the least.  So device text and pinned staging are bounded by max(SBX_TEXT_CHUNK_ENTRIES, the longest
     // row's weight) items, whatever the graph's size, and a call stays below the formatter's 2^32 items unless one row
-    // alone exceeds them.  The cuts are found by a binary search that reads single offsets of the device row_ptr.
+    // alone exceeds them.  The cuts are found by a binary search (detail::NextCut) that reads single offsets of the device
+    // row_ptr; rows weigh row_items at the least, which bounds the rows of a chunk.
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(SBX_TEXT_CHUNK_ENTRIES)), row_items = 1 + ncon;
     auto weight_at = [&](int64_t r) {
       NNZType o;
@@ -123,21 +123,11 @@ class MetisGraphWriter {
                                host_weights.empty() ? nullptr : d_weights.get(), ncon, base, precision, flags, o, cap, bytes);
     };
     for (int64_t b = row_begin; b < dim0;) {
-      // the last row end e in (b, hi] with weight(e) - weight(b) <= chunk; rows weigh row_items at the least
-      int64_t lo = b + 1, hi = std::min(dim0, b + std::max<int64_t>(1, chunk / row_items));
-      if (lo < hi) {
-        const int64_t limit = weight_at(b) + chunk;
-        if (weight_at(hi) <= limit) lo = hi;
-        while (lo + 1 < hi) {  // (weight(lo) <= limit or lo == b + 1; weight(hi) > limit)
-          const int64_t mid = lo + (hi - lo) / 2;
-          (weight_at(mid) <= limit ? lo : hi) = mid;
-        }
-      }
-      text.Chunk(out, b, lo - b, format);
-      b = lo;
+      const int64_t e = detail::NextCut(b, dim0, std::max<int64_t>(1, chunk / row_items), chunk, weight_at);
+      text.Chunk(out, b, e - b, format);
+      b = e;
     }
-    out.close();
-    if (!out) throw utils::WriterException("writing " + filename_ + " failed");
+    detail::CloseText(out, filename_);
   }
 
   std::string filename_;

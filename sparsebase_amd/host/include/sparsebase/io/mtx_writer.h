@@ -90,7 +90,7 @@ class MTXWriter {
       const int64_t count = (int64_t)arr->get_dimensions()[0];
       auto &dev = hip::Device::Get(hip::DefaultDevice());
       hip::Staged<ValueType> vals(dev, arr->get_vals(), (size_t)count);
-      std::ofstream out = Open();
+      std::ofstream out = detail::OpenText(filename_);
       out << "%%MatrixMarket " << object_ << " " << format_ << " " << field_ << " " << symmetry_ << "\n";
       out << 1 << " " << count << "\n";
       detail::TextStreamer text(dev);
@@ -99,7 +99,7 @@ class MTXWriter {
       text.Stream(out, count, [&](int64_t b, int64_t c, void *o, int64_t cap, int64_t *bytes) {
         return sbx_text_format_values(dev.handle(), hip::ValueTag<ValueType>(), c, v + b, precision, o, cap, bytes);
       });
-      Close(out);
+      detail::CloseText(out, filename_);
     }
   }
 
@@ -130,15 +130,6 @@ class MTXWriter {
       throw utils::WriterException("Matrix market writer does not currently support writing array as coordinate.");
     if (precision_ < 1 || precision_ > 17) throw utils::WriterException("precision: 1..17");
   }
-  std::ofstream Open() const {
-    std::ofstream out(filename_, std::ios::binary);
-    if (!out.is_open()) throw utils::WriterException("cannot open " + filename_ + " for writing");
-    return out;
-  }
-  void Close(std::ofstream &out) const {
-    out.close();
-    if (!out) throw utils::WriterException("writing " + filename_ + " failed");
-  }
 
   // row / col / val: device arrays of nnz entries (val may be null); every check, then the file
   void WriteDevice(const hip::Device &dev, int64_t n, int64_t m, int64_t nnz, const IDType *row, const IDType *col,
@@ -165,16 +156,16 @@ class MTXWriter {
       const int64_t bytes = text.Format([&](void *o, int64_t cap, int64_t *b) {
         return sbx_text_format_dense(dev.handle(), it, vt, n, m, nnz, row, col, val, precision, o, cap, b);
       });
-      std::ofstream out = Open();
+      std::ofstream out = detail::OpenText(filename_);
       out << "%%MatrixMarket " << object_ << " " << format_ << " " << field_ << " " << symmetry_ << "\n";
       out << n << " " << m << "\n";
       text.Flush(out, bytes);
-      Close(out);
+      detail::CloseText(out, filename_);
       return;
     }
     const unsigned flags = (field_ == "pattern" ? SBX_TEXT_PATTERN : 0u) | (said_symmetric ? SBX_TEXT_LOWER : 0u) |
                            (skew ? SBX_TEXT_NO_DIAGONAL : 0u);
-    std::ofstream out = Open();
+    std::ofstream out = detail::OpenText(filename_);
     out << "%%MatrixMarket " << object_ << " " << format_ << " " << field_ << " " << symmetry_ << "\n";
     out << n << " " << m << " " << size_nnz << "\n";
     constexpr size_t vb = hip::ValueBytes<ValueType>();
@@ -183,7 +174,7 @@ class MTXWriter {
                                         val ? (const void *)((const char *)val + (size_t)b * vb) : nullptr, 1, precision, flags, o,
                                         cap, bytes);
     });
-    Close(out);
+    detail::CloseText(out, filename_);
   }
 
   std::string filename_, object_, format_, field_, symmetry_;

@@ -98,8 +98,7 @@ class PatohWriter : public WritesHyperGraph<IDType, NNZType, ValueType> {
     };
     // without a cell-weight line the last net line is the file's last and loses its '\n' — unless it is empty
     const bool last_empty = nets > 0 && !ew && offset_at(nets) == offset_at(nets - 1);
-    std::ofstream out(filename_, std::ios::binary);
-    if (!out.is_open()) throw utils::WriterException("cannot open " + filename_ + " for writing");
+    std::ofstream out = detail::OpenText(filename_);
     const int scheme = (vw ? 1 : 0) | (ew ? 2 : 0);
     out << idx << ' ' << cells << ' ' << nets << ' ' << pins;  // patoh_writer.cc:122, :149, :188, :220
     if (scheme) out << ' ' << scheme;
@@ -113,28 +112,19 @@ class PatohWriter : public WritesHyperGraph<IDType, NNZType, ValueType> {
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(SBX_TEXT_CHUNK_ENTRIES));
     auto weight_at = [&](int64_t r) { return offset_at(r) + r; };
     for (int64_t b = 0; b < nets;) {
-      int64_t lo = b + 1, hi = std::min(nets, b + chunk);
-      if (lo < hi) {
-        const int64_t limit = weight_at(b) + chunk;
-        if (weight_at(hi) <= limit) lo = hi;
-        while (lo + 1 < hi) {  // (weight(lo) <= limit or lo == b + 1; weight(hi) > limit)
-          const int64_t mid = lo + (hi - lo) / 2;
-          (weight_at(mid) <= limit ? lo : hi) = mid;
-        }
-      }
-      const unsigned flags = (ew ? SBHG_NET_WEIGHTS : 0u) | ((lo == nets && !vw && !last_empty) ? SBHG_NO_LAST_NEWLINE : 0u);
-      text.Chunk(out, b, lo - b, [&](int64_t begin, int64_t count, void *o, int64_t cap, int64_t *bytes) {
+      const int64_t e = detail::NextCut(b, nets, chunk, chunk, weight_at);
+      const unsigned flags = (ew ? SBHG_NET_WEIGHTS : 0u) | ((e == nets && !vw && !last_empty) ? SBHG_NO_LAST_NEWLINE : 0u);
+      text.Chunk(out, b, e - b, [&](int64_t begin, int64_t count, void *o, int64_t cap, int64_t *bytes) {
         return sbhg_patoh_format(dev.handle(), it, vt, begin, begin + count, xpin, pin, ew ? d_nw.get() : nullptr, delta,
                                  precision, flags, o, cap, bytes);
       });
-      b = lo;
+      b = e;
     }
     if (vw)
       text.Stream(out, cells, [&](int64_t begin, int64_t count, void *o, int64_t cap, int64_t *bytes) {
         return sbhg_patoh_format_weights(dev.handle(), vt, begin, begin + count, d_cw.get(), precision, o, cap, bytes);
       });
-    out.close();
-    if (!out) throw utils::WriterException("writing " + filename_ + " failed");
+    detail::CloseText(out, filename_);
   }
 
   std::string filename_;

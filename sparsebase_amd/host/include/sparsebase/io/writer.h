@@ -1,4 +1,4 @@
-// sparsebase/io/writer.h — what the two text writers share (reference: io/writer.h declares the WritesCOO / WritesCSR /
+// sparsebase/io/writer.h — what the text writers share (reference: io/writer.h declares the WritesCOO / WritesCSR /
 // WritesArray interfaces; here the shared part is how device text reaches a file).
 //
 // The text is produced on the device by the formatters of include/sbx_text.h and leaves it in chunks of
@@ -10,6 +10,7 @@
 #define SPARSEBASE_IO_WRITER_H_
 #include <algorithm>
 #include <cstdint>
+#include <fstream>
 #include <ostream>
 #include <string>
 
@@ -25,6 +26,34 @@ namespace sparsebase::io::detail {
 
 inline void WriterCheck(const hip::Device &dev, int rc) {
   if (rc != SBX_OK) throw utils::WriterException(std::string("text writer: ") + sbx_last_error(dev.handle()));
+}
+
+// the file a writer fills, and its end: closed, and whatever went wrong on the way reported
+inline std::ofstream OpenText(const std::string &filename) {
+  std::ofstream out(filename, std::ios::binary);
+  if (!out.is_open()) throw utils::WriterException("cannot open " + filename + " for writing");
+  return out;
+}
+inline void CloseText(std::ofstream &out, const std::string &filename) {
+  out.close();
+  if (!out) throw utils::WriterException("writing " + filename + " failed");
+}
+
+// For the writers that cut their chunks themselves (rows of unequal length): the end of the longest run of rows from b,
+// of max_rows rows and up to `end` at the most, that weighs at most `chunk` — one row at the least.  weight_at(r) is the
+// weight of the rows before r, ascending; it is read at b and at O(log max_rows) places more.
+template <typename W>
+int64_t NextCut(int64_t b, int64_t end, int64_t max_rows, int64_t chunk, W weight_at) {
+  int64_t lo = b + 1, hi = std::min(end, b + max_rows);
+  if (lo < hi) {
+    const int64_t limit = weight_at(b) + chunk;
+    if (weight_at(hi) <= limit) lo = hi;
+    while (lo + 1 < hi) {  // (weight(lo) <= limit or lo == b + 1; weight(hi) > limit)
+      const int64_t mid = lo + (hi - lo) / 2;
+      (weight_at(mid) <= limit ? lo : hi) = mid;
+    }
+  }
+  return lo;
 }
 
 class TextStreamer {
