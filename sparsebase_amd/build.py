@@ -35,6 +35,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbhg.h"))
     hs.append(os.path.join(ROOT, "include", "sbfx.h"))
     hs.append(os.path.join(ROOT, "include", "sbsym.h"))
+    hs.append(os.path.join(ROOT, "include", "sbmv.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

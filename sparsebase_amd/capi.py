@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h, include/sbfx.h and include/sbsym.h
+include/sbhg.h, include/sbfx.h, include/sbsym.h and include/sbmv.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -189,6 +189,13 @@ SYM_PROTOTYPES = {
                               C.POINTER(_i64)], _int),
 }
 
+# every symbol include/sbmv.h declares (tests/test_mv_abi.py checks header <-> library <-> this table): the CSR
+# matrix-vector product and its input check, prefix `sbmv_`
+MV_PROTOTYPES = {
+    "sbmv_csr_check": ([_H, _int, _i64, _i64, _i64, _vp, _vp], _int),
+    "sbmv_csr_spmv": ([_H, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int),
+}
+
 _lib = None
 
 
@@ -203,7 +210,8 @@ def load():
         for name, (argtypes, restype) in (list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) +
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
-                                           list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items())):
+                                           list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items()) +
+                                           list(MV_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

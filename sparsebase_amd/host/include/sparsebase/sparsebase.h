@@ -7,6 +7,9 @@
 #include "sparsebase/context/hip_context.h"
 #include "sparsebase/converter/converter_order_one.h"
 #include "sparsebase/converter/converter_order_two.h"
+#include "sparsebase/experiment/concrete_experiment.h"
+#include "sparsebase/experiment/experiment_helper.h"
+#include "sparsebase/experiment/experiment_type.h"
 #include "sparsebase/format/array.h"
 #include "sparsebase/feature/avg_degree.h"
 #include "sparsebase/feature/avg_degree_column.h"
@@ -34,6 +37,7 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/kernels/spmv.h"
 #include "sparsebase/reorder/boba_reorder.h"
 #include "sparsebase/reorder/reorder_heatmap.h"
 #include "sparsebase/reorder/slashburn_reorder.h"

@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -452,6 +452,34 @@ def csr_symmetrize(row_ptr, col, val=None, no_diagonal=False):
     opaque payloads.  no_diagonal drops the stored (i, i).  See sbsym_csr_symmetrize in include/sbsym.h."""
     hd = handle_for(_check_dev(row_ptr, col, val))
     return _csr_symmetrize(hd, row_ptr, col, val, capi.SYM_NO_DIAGONAL if no_diagonal else 0)
+
+
+# ----------------------------------------------------------------------------- y = A x (include/sbmv.h)
+def csr_check(row_ptr, col, m):
+    """Raises capi.SbxError (bad argument; the message names what failed and where) unless (row_ptr, col) is a
+    well-formed CSR with m columns: row_ptr[0] == 0, row_ptr non-decreasing, row_ptr[n] == nnz, every column in [0, m).
+    Synchronous.  See sbmv_csr_check in include/sbmv.h."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    hd.check(hd.lib.sbmv_csr_check(hd.h, _it(row_ptr, col), row_ptr.numel() - 1, int(m), col.numel(), _p(row_ptr), _p(col)))
+
+
+def csr_spmv(row_ptr, col, x, val=None, m=None, out=None):
+    """y = A x of a CSR matrix: a device tensor of n values of x's dtype (float32, float64, int32 or int64; integers wrap).
+    val=None is a pattern matrix (every stored value 1); m defaults to x.numel().  Deterministic and asynchronous; an
+    entry whose column lies outside [0, m) contributes nothing.  See sbmv_csr_spmv in include/sbmv.h."""
+    hd = handle_for(_check_dev(row_ptr, col, x, val, out))
+    n = row_ptr.numel() - 1
+    m = x.numel() if m is None else int(m)
+    if m > x.numel():
+        raise ValueError(f"x holds {x.numel()} values, the matrix has {m} columns")
+    if val is not None and (val.dtype != x.dtype or val.numel() != col.numel()):
+        raise TypeError("val must have the dtype of x and one value per stored entry")
+    y = torch.empty(n, dtype=x.dtype, device=x.device) if out is None else out
+    if y.dtype != x.dtype or y.numel() != n:
+        raise TypeError("out must have the dtype of x and one value per row")
+    hd.check(hd.lib.sbmv_csr_spmv(hd.h, _it(row_ptr, col), _vt(x), n, m, col.numel(), _p(row_ptr), _p(col), _p(val), _p(x),
+                                  _p(y)))
+    return y
 
 
 def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
