@@ -58,6 +58,7 @@ const sbx_switches &sbx_sw() {
     w.tie_single = std::min((unsigned)integer("SBX_DEBUG_TIE_SINGLE", TS_SINGLE), TS_SINGLE);
     w.tie_cap = std::min((unsigned)integer("SBX_DEBUG_TIE_CAP", TS_CAP), TS_CAP);
     w.tie_walk_debug = present("SBX_DEBUG_TIE_WALK");
+    w.rcm_level_paths = present("SBX_DEBUG_RCM_LEVEL_PATHS");
     w.rcm_check = off_unless_set("SBX_DEBUG_RCM_CHECK");
     w.chain_tail_abort = off_unless_set("SBX_DEBUG_CHAIN_TAIL_ABORT");
     w.permute_overlap = on_unless_0("SBX_PERMUTE_OVERLAP");

@@ -232,6 +232,7 @@ struct sbx_switches {
   unsigned tie_single;       // SBX_DEBUG_TIE_SINGLE, TS_SINGLE (at most): entries above which a step goes to the grid
   unsigned tie_cap;          // SBX_DEBUG_TIE_CAP, TS_CAP (at most): members of a level the tie walk takes
   bool tie_walk_debug;       // SBX_DEBUG_TIE_WALK, off; set at all: the walk's exit is printed, no speculative sweep
+  bool rcm_level_paths;      // SBX_DEBUG_RCM_LEVEL_PATHS, off; set at all: run_bfs prints how it orders each level above 4096
   bool rcm_check;            // SBX_DEBUG_RCM_CHECK, off; non-zero: every unordered sweep is checked, its trace printed
   bool chain_tail_abort;     // SBX_DEBUG_CHAIN_TAIL_ABORT, off; non-zero: a chain's tail run gives up at once
   // Permute2D and CSR row sort (sbx_permute.hip)

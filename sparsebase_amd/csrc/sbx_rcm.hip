@@ -2293,6 +2293,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
       sbx_radix_pass passes[16];
       int np;
       int low_bits = 32;  // width of the key's low field (vertex id or degree rank); 32: the parent position starts at bit 32
+      const char *route;  // which of the seven ways orders this level (SBX_DEBUG_RCM_LEVEL_PATHS prints it)
       if (sbx_sw().rcm_count_sort && (int64_t)nf <= RCM_COUNT_SORT_MAX) {
         // The level's vertices in the order of their low key field — ascending degree rank (Cuthill-McKee) or id
         // (plain) — read off a bitmap, so that only the parent positions are left to sort, stably, by the counting
@@ -2302,14 +2303,17 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
         const int64_t words = (span + 63) / 64;
         const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
         if (!CM && !set_bits) {
+          route = "count:fresh";
           SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words, dim3((unsigned)fw_blocks), dim3(256), (const unsigned *)b.ppos,
                       (unsigned long long *)b.vbits,
                       mark_frontier ? (unsigned long long *)b.fbits : (unsigned long long *)nullptr, b.fresh64, b.wcnt,
                       b.woff, b.n);
         } else if (CM && (int64_t)nf * 16 >= b.n_ranked) {  // (a scattered bit costs ~16 gathered ones)
+          route = "count:fresh_ranked";
           SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words_ranked, dim3((unsigned)fw_blocks), dim3(256),
                       (const unsigned *)b.ppos, (const unsigned *)b.vbits, b.dorder, b.fresh64, b.wcnt, b.woff, b.n_ranked);
         } else {
+          route = "count:scatter";
           SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_scatter, dim3(g), dim3(256), (const I *)b.nf_list, nf,
                       CM ? b.drank : (const uint32_t *)nullptr, b.fresh64);
           SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_counts, dim3((unsigned)fw_blocks), dim3(64),
@@ -2328,6 +2332,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
         np = -1;  // ordered
       } else if (!CM && !set_bits) {
         // keys in ascending id order straight from the bitmap pass: only the parent positions are left to sort
+        route = "radix:fresh";
         const int64_t words = (b.n + 63) / 64;
         const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
         SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words, dim3((unsigned)fw_blocks), dim3(256), (const unsigned *)b.ppos,
@@ -2343,6 +2348,7 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
         np = sbx_radix_plan(0, 0, 32, 32 + sbx_bits_for((uint64_t)(fsize - 1)), passes);
       } else if (CM && !set_bits && sbx_sw().rcm_ranked_keys && (int64_t)nf * sbx_sw().rcm_ranked_div >= b.n_ranked) {
         // keys in ascending degree-rank order from a bitmap in rank space: only the parent positions are left to sort
+        route = "radix:fresh_ranked";
         const int64_t words = (b.n_ranked + 63) / 64;
         const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
         SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words_ranked, dim3((unsigned)fw_blocks), dim3(256),
@@ -2354,11 +2360,16 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
                     (const unsigned *)b.ppos, b.dorder, b.ka, (uint32_t *)nullptr, (uint32_t *)nullptr, words, b.dv);
         np = sbx_radix_plan(0, 0, 32, 32 + sbx_bits_for((uint64_t)(fsize - 1)), passes);
       } else {
+        route = "radix:full";
         low_bits = sbx_bits_for((uint64_t)(b.n - 1));
         SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_keys<CM>), dim3(g), dim3(256), (const I *)b.nf_list, nf,
                     (const unsigned *)b.ppos, b.drank, b.ka, b.dv, low_bits);
         np = sbx_radix_plan(0, low_bits + sbx_bits_for((uint64_t)(fsize - 1)), 0, 0, passes);
       }
+      if (sbx_sw().rcm_level_paths)  // (passes: digit passes of the radix sort, or of the counting sort: 9 bits each)
+        fprintf(stderr, "[rcm level-path] sweep=%s level=%u fsize=%u nf=%u route=%s passes=%d set_bits=%d mark_frontier=%d\n",
+                CM ? "cm" : "plain", level + 1, fsize, nf, np == 0 ? "emit_only" : route,
+                np < 0 ? (std::max(sbx_bits_for((uint64_t)(fsize - 1)), 1) + 8) / 9 : np, set_bits, mark_frontier);
       if (np < 0) {
       } else if (np > 0) {
         // the last digit pass writes the queue, the bits and the level positions itself (no pass over sorted keys)

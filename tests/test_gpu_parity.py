@@ -1593,7 +1593,12 @@ def test_rcm_cuthill_mckee_level_keys_in_a_child(mode):
     of the ranked vertices on — by keys read off a bitmap in RANK space, already in degree-rank order, of which only the
     parent-position digits are sorted (sbx_rcm.hip: k_fresh_words_ranked).  Graphs with levels of 10^5 .. 10^6 vertices;
     SBX_DEBUG_RCM_RANKED_DIV=100000 sends every level that takes the bitmap pass that way, SBX_RCM_RANKED_KEYS=0 none.
-    (Read once per process, hence the children.)"""
+    (Read once per process, hence the children.)
+    Since the counting sort of sbx_countsort.h both switches are read only behind it — with SBX_RCM_COUNT_SORT=0, or for a
+    level above 2^20 vertices.  No level of these graphs is that wide, so both modes run what no switch at all runs: the
+    test still holds these orders to the reference, it no longer chooses between the two kinds of keys.  The two kinds
+    (and every other way a level above 4096 vertices is ordered) are pinned, with the proof that they ran, by
+    tests/test_rcm_level_order_gpu.py."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
