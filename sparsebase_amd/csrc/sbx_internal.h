@@ -123,6 +123,17 @@ struct sbx_aux_scope {
   sbx_aux_scope(const sbx_aux_scope &) = delete;
   sbx_aux_scope &operator=(const sbx_aux_scope &) = delete;
 };
+// Work enqueued on a side stream: h->stream is that stream while the guard lives and the previous one again on every
+// way out of its block, so the launches inside go through SBX_KLAUNCH / SBX_HIP / SBX_TRY like any others.  (The fork
+// and join events, and aux_dirty, stay with the caller.)
+struct sbx_stream_scope {
+  sbx_handle_t h;
+  hipStream_t prev;
+  sbx_stream_scope(sbx_handle_t h_, hipStream_t side) : h(h_), prev(h_->stream) { h->stream = side; }
+  ~sbx_stream_scope() { h->stream = prev; }
+  sbx_stream_scope(const sbx_stream_scope &) = delete;
+  sbx_stream_scope &operator=(const sbx_stream_scope &) = delete;
+};
 void sbx_prof_begin(sbx_handle_t h, int kid);
 void sbx_prof_end(sbx_handle_t h);
 

@@ -35,7 +35,6 @@
 #include <utility>
 #include <algorithm>
 #include <vector>
-#include <functional>
 #include <string>
 
 namespace {
@@ -2063,68 +2062,6 @@ __global__ __launch_bounds__(256) void k_write_component(const I *__restrict__ q
 
 constexpr int64_t RCM_COUNT_SORT_MAX = (int64_t)1 << 20;  // levels above this: the generic sort's staged stores win
 
-struct BfsBuffers {
-  bool *claim_clean;  // the claim bytes of the unordered sweeps are all zero (a finished sweep leaves them that way)
-  const X *rp, *col;
-  unsigned *vbits, *fbits, *lpos, *ppos;
-  const unsigned *ebits;  // bit v: row v is empty (k_deg_count, at the head of the call on the caller's stream)
-  const I *label;
-  int64_t nnz;
-  I *q;         // visiting order of the current BFS (levels concatenated)
-  I *nf_list;   // unordered next frontier
-  uint64_t *heavy;
-  uint64_t heavy_cap;  // descriptors the queue holds
-  uint2 *hub_dir;  // per workgroup of k_bfs_expand: (first chunk descriptor, count)
-  uint64_t *ka, *kb;
-  unsigned long long *fresh64;  // per 64 vertices: the bits the current level added to the visited bitmap
-  int *wcnt, *woff;             // ... their popcounts, and the totals of every RCM_FW_WORDS of them
-  unsigned *cs_scratch;         // the level ordering's counting sort (sbx_cs::scratch_words(n) words)
-  const uint32_t *drank, *dorder;
-  int64_t n_ranked;  // entries of dorder (vertices with a non-empty row)
-  RcmDev *dv;
-  int64_t n;
-  unsigned max_deg;  // largest degree of the graph: no hub kernel launches when nothing exceeds RCM_LIGHT
-  // the call's first read-back rides on the first sweep's (saves a round trip at the head of every call): when set, the
-  // first read-back of run_ubfs also delivers the degree counts k_deg_reduce left (max_deg above is not known before)
-  RcmDev *late_counts;
-  bool *late_counts_ready;
-  // work the host still has to enqueue elsewhere (the degree ranks on their side stream): run once, right after a sweep's
-  // first launch and before the host waits for it, so that its enqueue time hides behind the kernel (bfs_first_launch)
-  std::function<int()> *after_first_launch;
-  // the hook enqueues a dozen launches or more (~5 us of host time each): it is only run where the GPU has that much
-  // work in front of the next read-back — a chain of big levels (run_ubfs) or an ordered sweep's launches — and not
-  // behind a 40 us kernel, which it would outlast with the caller's stream idle
-  bool hook_wants_long_cover;
-  // an unordered sweep enqueues its first chain of big levels right behind its head small-level run (run_ubfs): set for
-  // the call's first sweep only — it starts at the first non-empty row, the later ones at a vertex of smallest degree in
-  // a deepest level, whose first big frontier is a thin one for the top-down kernels (the chain's launches would all
-  // leave at once, ~35 us of empty launches; measured on the bench matrix, NOTES section 4.5-r6)
-  bool head_chain;
-  // the tie-break in front of this sweep was left unverified (ubfs_pick_root): the sweep's first read-back says whether
-  // the walk named the root (tie_done) — if not, the sweep's first kernels have left (RcmDev::spec_guard), the sweep
-  // returns with *spec_failed set and the caller lets the persistent cone kernels finish the tie-break
-  bool *tie_unverified;
-  // the labelling of the other components runs on a side stream (sbx_rcm_reorder); its counters live in *dv.  Once both
-  // of its halves are enqueued (*side_stage >= 2) a Cuthill-McKee sweep joins that stream at its start — the work
-  // finished long before — so that the sweep's own last read-back of *dv also delivers those counters (*last_read,
-  // *last_read_joined) and the call needs no read-back of its own for them
-  const int *side_stage;
-  hipEvent_t side_event;
-  bool *side_joined;
-  RcmDev *last_read;
-  bool *last_read_joined;
-};
-
-// the grid of a bottom-up level: 32 waves per CU, all resident (see RCM_BU_WAVES)
-static unsigned bu_grid(sbx_handle_t h) { return (unsigned)h->num_cus * (unsigned)RCM_BU_WG_PER_CU; }
-
-// cover_us: roughly how long the kernels just enqueued keep the GPU busy before the host's next read-back returns
-static int bfs_first_launch(const BfsBuffers &b, int cover_us = 1000) {  // (the hook ignores every call after its last stage)
-  if (!b.after_first_launch) return SBX_OK;
-  if (b.hook_wants_long_cover && cover_us < 100) return SBX_OK;
-  return (*b.after_first_launch)();
-}
-
 struct BfsResult {
   unsigned count;        // vertices reached
   unsigned levels;       // number of levels (eccentricity + 1)
@@ -2132,36 +2069,356 @@ struct BfsResult {
   unsigned last_size;
 };
 
+struct Searched {  // what search_component leaves: the last sweep (the component's order is in q), the search's statistics
+  BfsResult r;
+  int64_t sweeps, levels, candidate;
+  bool cm_done;
+};
+
+// One call of sbx_rcm_reorder: its arguments, its buffers (arena memory, gone with the call) and everything the host
+// knows about the call so far.  The sweeps, the tie-break and the steps of the entry function all work on this.
+struct RcmCall {
+  sbx_handle_t h;
+  const X *rp, *col;
+  X *inv;
+  int64_t n, nnz;
+  // ---- buffers (alloc_buffers)
+  RcmDev *dv;
+  uint32_t *did_a, *drank;
+  I *label_buf, *csize, *cbase, *small_list, *mid_list, *large_list, *big_list, *q_small;
+  I *q;         // visiting order of the current BFS (levels concatenated)
+  I *nf_list;   // unordered next frontier
+  unsigned *dist, *ppos, *vbits, *fbits, *cbits, *lpos;
+  unsigned *ebits;  // bit v: row v is empty (k_deg_count, at the head of the call on the caller's stream): with vbits,
+                    // the candidates of every bottom-up level
+  uint64_t *heavy, *ka, *kb;
+  uint64_t heavy_cap;  // descriptors the queue (heavy) holds
+  unsigned *ucnt;   // per unit: non-empty rows, largest degree, first non-empty vertex, rows of 255+ entries
+  uint2 *hub_dir;   // per workgroup of k_bfs_expand: (first chunk descriptor, count)
+  unsigned long long *fresh64;  // per 64 vertices: the bits the current level added to the visited bitmap
+  int *wcnt, *woff;             // ... their popcounts, and the totals of every RCM_FW_WORDS of them
+  unsigned *cs_scratch;         // the level ordering's counting sort (sbx_cs::scratch_words(n) words)
+  unsigned char *claim8;        // the unordered sweeps' claim bytes
+  unsigned *nbits, *cone;       // the bitmap a bottom-up level of an unordered sweep writes; the tie-break's cone
+  unsigned gn;      // grid of the passes over all n vertices
+  size_t bm_bytes;  // bytes of one bitmap over the vertices
+  const uint32_t *dorder = nullptr;  // vertices by ascending (degree, id): set once the ranks are enqueued
+  const I *label = nullptr;          // component labels: set once the labelling has finished
+  // ---- the degree counts k_deg_reduce left.  The call's first read-back rides on the first sweep's (saves a round trip
+  // at the head of every call): with lazy_counts the first read-back of run_ubfs also delivers them (take_counts)
+  bool unordered_ok, lazy_counts, counts_ready = false;
+  RcmDev counts;
+  int64_t n_ranked = 0;  // entries of dorder (vertices with a non-empty row)
+  unsigned max_deg = 0;  // largest degree of the graph: no hub kernel launches when nothing exceeds RCM_LIGHT
+  void take_counts(const RcmDev &d) { counts = d, counts_ready = true, n_ranked = (int64_t)d.n_nonempty, max_deg = d.max_deg; }
+  // ---- side streams: the degree ranks on aux_stream[0], the labelling of the other components on aux_stream[1]
+  hipStream_t main_stream;
+  bool side;  // the side streams are in use (no profiler, SBX_RCM_OVERLAP)
+  bool ranks_enqueued = false, ranks_joined = false;
+  // the labelling of the other components is running on a side stream of its own while the first component is searched
+  // (label_rest): its counters live in *dv.  Once both of its halves are enqueued (cc_stage >= 2) a Cuthill-McKee sweep
+  // joins that stream at its start — the work finished long before — so that the sweep's own last read-back of *dv also
+  // delivers those counters (last_read, last_read_joined) and the call needs no read-back of its own for them
+  bool cc_forked = false, cc_joined = false, last_read_joined = false;
+  int cc_stage = 0;  // halves of the labelling enqueued so far
+  RcmDev last_read;
+  bool claim_clean = false;  // the claim bytes of the unordered sweeps are all zero (a finished sweep leaves them that way)
+  // an unordered sweep enqueues its first chain of big levels right behind its head small-level run (run_ubfs): set for
+  // the call's first sweep only — it starts at the first non-empty row, the later ones at a vertex of smallest degree in
+  // a deepest level, whose first big frontier is a thin one for the top-down kernels (the chain's launches would all
+  // leave at once, ~35 us of empty launches; measured on the bench matrix, NOTES section 4.5-r6)
+  bool head_chain = true;
+  // the tie-break in front of this sweep was left unverified (ubfs_pick_root): the sweep's first read-back says whether
+  // the walk named the root (tie_done) — if not, the sweep's first kernels have left (RcmDev::spec_guard), the sweep
+  // returns with *spec_failed set and the caller lets the persistent cone kernels finish the tie-break
+  bool tie_unverified = false;
+  int64_t unordered_sweeps = 0;  // sweeps that kept the level sets only (statistics; the tests check the path was taken)
+  // ---- the first sweep and what the labelling found (first_sweep, label_rest)
+  I v0;  // the first non-empty row (-1: not one edge)
+  BfsResult r0 = {};
+  Searched sd0;
+  bool r0_unordered = false, comp0_searched = false, small_on_side = false, single_component = false;
+  RcmDev hd = {};  // the labelling's counters
+  bool mid_batched = false, first_is_large = false;
+  unsigned n_host = 0;  // components ordered from the host
+  int64_t sweeps_max = 0, levels_max = 0, largest = 0, ref_sweeps_max = 0;
+  // Work the host still has to enqueue elsewhere: run right after a sweep's first launch and before the host waits for it,
+  // so that its enqueue time hides behind the kernel (bfs_first_launch).  While the first component is searched beside
+  // its labelling: the degree ranks and one half of the labelling per firing (nothing once both halves are out);
+  // otherwise the degree ranks alone.
+  int after_first_launch() { return cc_forked ? enqueue_cc() : enqueue_ranks(); }
+  // the hook enqueues a dozen launches or more (~5 us of host time each, the ranks: ~15 launches): it is only run where
+  // the GPU has that much work in front of the next read-back — a chain of big levels (run_ubfs) or an ordered sweep's
+  // launches — and not behind a 40 us kernel, which it would outlast with the caller's stream idle.  (The labelling's
+  // halves: half a dozen launches per call.)
+  bool hook_wants_long_cover() const { return !cc_forked; }
+  // Only the Cuthill-McKee sweep reads the degree ranks: they are built on a side stream while the plain sweeps —
+  // launch- and latency-bound — run on the caller's stream, and joined before the first Cuthill-McKee sweep.
+  int enqueue_ranks() {
+    if (ranks_enqueued) return SBX_OK;
+    ranks_enqueued = true;
+    dorder = did_a;
+    sbx_stream_scope on_side(h, side ? h->aux_stream[0] : h->stream);
+    if (side) {
+      void *slot = nullptr;
+      SBX_TRY(sbx_arena_alloc(h, SBX_RS_SLOT_BYTES, &slot));
+      SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[0], h->aux_event[0], 0));
+      h->aux_dirty = true;
+      SBX_HIP(h, hipMemsetAsync(slot, 0, SBX_RS_SLOT_BYTES, h->stream));
+      h->rs_override = slot;
+    }
+    // one stable counting pass on min(degree, 255) over the rows in id order + the last bucket by its full degree
+    // (sbx_degree.hip): 0.09 ms where a generic sort of (degree, id) pairs took 0.31
+    // (counts — not what take_counts derived from it: this may run inside the first sweep, right behind the read-back that
+    // delivered the counts)
+    const int rc = sbx_degree_ranks(h, SBX_RCM_IT, rp, n, (int64_t)counts.n_nonempty, (int64_t)counts.n_top,
+                                    counts.max_deg, drank, did_a);
+    h->rs_override = nullptr;
+    SBX_TRY(rc);
+    if (side) SBX_HIP(h, hipEventRecord(h->aux_event[1], h->stream));
+    return SBX_OK;
+  }
+  int join_ranks() {
+    if (!ranks_enqueued) SBX_TRY(enqueue_ranks());
+    if (!ranks_joined) {
+      SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[1], 0));
+      ranks_joined = true;
+      if (!cc_forked) h->aux_dirty = false;
+    }
+    return SBX_OK;
+  }
+
+  // (3) connected components of the rest; the root of each tree is the component's smallest id
+  // (in two halves: on the side stream each half is enqueued behind one of the tie-break's ~45 us kernels; 2: both)
+  int enqueue_cc_kernels(int half) {
+    const unsigned gcount = gn < 1024u ? gn : 1024u;
+    if (half != 1) {
+      SBX_KLAUNCH(h, SBX_K_CC, k_cc_init, dim3(gn), dim3(256), rp, col, label_buf, n, (const unsigned *)cbits);
+      SBX_KLAUNCH(h, SBX_K_CC, k_cc_hook_small, dim3(gn), dim3(256), rp, col, label_buf, n, big_list,
+                  (const unsigned *)cbits, dv);
+      SBX_KLAUNCH(h, SBX_K_CC, k_cc_hook_big, dim3((unsigned)h->num_cus * 8), dim3(256), rp, col, label_buf,
+                  (const I *)big_list, (const RcmDev *)dv);
+      // (phase 0 and the classification end in one counter add per workgroup: few workgroups, or the counter word is the
+      // bottleneck — 16 K adds on one word cost 0.19 ms)
+      for (int phase = 0; phase < 2; phase++)
+        SBX_KLAUNCH(h, SBX_K_CC, k_cc_finalize, dim3(phase == 0 ? gcount : gn), dim3(256), rp, label_buf, csize, n,
+                    (const unsigned *)cbits, v0 >= 0 ? v0 : (I)0, (I)r0.count, phase, dv);
+      SBX_LAUNCH_CHECK(h);
+    }
+    if (half != 0) {
+      SBX_TRY(sbx_exclusive_scan_i32(h, csize, cbase, n + 1, nullptr));
+      SBX_KLAUNCH(h, SBX_K_CC, k_classify, dim3(gcount), dim3(256), (const I *)label_buf, (const I *)csize,
+                  (const I *)cbase, inv, small_list, mid_list, large_list, n, dv);
+      SBX_LAUNCH_CHECK(h);
+    }
+    return SBX_OK;
+  }
+  // The next half of the labelling on its side stream, behind the degree ranks on theirs.
+  // (a half per firing, behind any launch: both halves at one go behind a chain of big levels only — tried when the
+  // tie-breaks stopped being 80 us of persistent kernels to hide behind — looked better under the profiler, whose
+  // launches take 10 us of host time each, and cost 28 us on the wall clock: the side work simply started later)
+  int enqueue_cc() {
+    SBX_TRY(enqueue_ranks());
+    if (cc_stage >= 2) return SBX_OK;
+    if (cc_stage == 0) SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[2], 0));
+    sbx_stream_scope on_side(h, h->aux_stream[1]);
+    const int half = cc_stage++;
+    SBX_TRY(enqueue_cc_kernels(half));
+    if (half == 1) {  // the small components too: their number stays on the device, the launch covers any
+      const unsigned lanes = (unsigned)std::min<int64_t>((n / 2 + 63) / 64 * 64, (int64_t)h->num_cus * 32 * 64);
+      SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3(lanes / 64 > 0 ? lanes / 64 : 1), dim3(64), rp, col,
+                  (const I *)small_list, 0u, (const I *)csize, (const I *)cbase, dist, q_small, inv, dv,
+                  (const unsigned *)&dv->n_small);
+      SBX_LAUNCH_CHECK(h);
+      SBX_HIP(h, hipEventRecord(h->aux_event[3], h->stream));
+    }
+    return SBX_OK;
+  }
+};
+
+// the grid of a bottom-up level: 32 waves per CU, all resident (see RCM_BU_WAVES)
+static unsigned bu_grid(sbx_handle_t h) { return (unsigned)h->num_cus * (unsigned)RCM_BU_WG_PER_CU; }
+
+// the grid of a top-down level: four waves per workgroup, RCM_VPW frontier vertices per wave, at most 8 workgroups per CU
+static unsigned topdown_grid(sbx_handle_t h, unsigned fsize) {
+  const unsigned waves_needed = (fsize + RCM_VPW - 1) / RCM_VPW;
+  return std::min(std::max((waves_needed + 3) / 4, 1u), (unsigned)h->num_cus * 8);
+}
+
+// the hub kernel (mode U) runs as exactly one resident wave of workgroups: a partial second wave (x8 on a kernel that
+// fits 5 per CU) left a tail that cost 15 %
+template <int U>
+static unsigned heavy_grid(sbx_handle_t h) {
+  static int per_cu = 0;  // (asked once per process)
+  if (per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bfs_expand_heavy<U>, 256, 0) != hipSuccess ||
+                      per_cu < 1))
+    per_cu = 4;
+  return (unsigned)h->num_cus * (unsigned)per_cu;
+}
+
+// cover_us: roughly how long the kernels just enqueued keep the GPU busy before the host's next read-back returns
+static int bfs_first_launch(RcmCall &c, int cover_us = 1000) {
+  if (c.hook_wants_long_cover() && cover_us < 100) return SBX_OK;
+  return c.after_first_launch();
+}
+
+// A sweep's first read-back (see RcmCall::tie_unverified): when the tie walk in front of the sweep had left without
+// naming the root, *spec_failed is set — the sweep's first kernels have left too, and the sweep returns at once.
+static int check_tie_walk(sbx_handle_t h, RcmCall &c, const RcmDev &hd, bool *spec_failed, const char *sweep) {
+  if (!c.tie_unverified) return SBX_OK;
+  c.tie_unverified = false;
+  if (hd.tie_done) return SBX_OK;
+  if (!spec_failed)
+    SBX_FAIL(h, SBX_ERR_INTERNAL, "%s: an unverified tie-break in front of a sweep that cannot be redone", sweep);
+  *spec_failed = true;
+  return SBX_OK;
+}
+
+// How one level of an ordered sweep is put in order — by parent position, then by the key's low field: the degree rank
+// (Cuthill-McKee) or the vertex id (plain).  Decided first (level_route), launched from the decision (order_level).
+// Where the order of the low field comes from: a bitmap the pass over ppos built in id space (KEYS_FRESH) or in rank
+// space (KEYS_FRESH_RANKED), or one the level's own list scattered into (KEYS_SCATTER) — read off any of them the
+// vertices come in ascending order of that field and only the parent positions are left to sort — or full keys.
+enum LevelKeys { KEYS_FRESH, KEYS_FRESH_RANKED, KEYS_SCATTER, KEYS_FULL };
+// The one-workgroup LDS sort of a small level; the counting sort of sbx_countsort.h (stable, three small launches per
+// 9-bit digit); the radix sort; nothing to sort (one parent and keys already in order: the emit kernel alone).
+enum LevelSorter { SORT_LDS, SORT_COUNTING, SORT_RADIX, SORT_EMIT_ONLY };
+struct LevelRoute {
+  LevelKeys keys;
+  LevelSorter sorter;
+  bool bitmap_pass;  // wide enough for a pass over ppos (k_fresh_words / k_visited_from_ppos): all of fbits is rewritten
+  int set_bits;      // the level's vertices set their visited (and frontier) bits one by one: no bitmap pass
+  int mark_frontier;  // the next expansion is bottom-up: the frontier bitmap and the level positions are written too
+  int low_bits;      // width of the key's low field (vertex id or degree rank); 32: the parent position starts at bit 32
+  int np;            // digit passes of the radix sort
+  sbx_radix_pass passes[16];
+  const char *name;  // which of the seven ways orders this level (SBX_DEBUG_RCM_LEVEL_PATHS prints it)
+};
+
+template <bool CM>
+static LevelRoute level_route(const RcmCall &c, unsigned fsize, unsigned nf, int mark_frontier) {
+  LevelRoute r;
+  r.mark_frontier = mark_frontier;
+  r.bitmap_pass = nf > (unsigned)RCM_LDS_SORT && (int64_t)nf >= std::max<int64_t>(RCM_REBUILD_BITS, c.n / 128);
+  r.set_bits = r.bitmap_pass ? 0 : 1;  // one pass over ppos (n words) against one single-bit atomic per vertex of the level
+  r.keys = KEYS_FULL, r.low_bits = 32, r.np = 0, r.name = "lds";
+  if (nf <= RCM_LDS_SORT) {
+    r.sorter = SORT_LDS;
+  } else if (sbx_sw().rcm_count_sort && (int64_t)nf <= RCM_COUNT_SORT_MAX) {
+    // The bitmap comes from a pass over all (ranked) vertices when the level holds a good part of them, from the
+    // level's own list otherwise.
+    r.sorter = SORT_COUNTING;
+    if (!CM && !r.set_bits) r.keys = KEYS_FRESH, r.name = "count:fresh";
+    else if (CM && (int64_t)nf * 16 >= c.n_ranked)  // (a scattered bit costs ~16 gathered ones)
+      r.keys = KEYS_FRESH_RANKED, r.name = "count:fresh_ranked";
+    else r.keys = KEYS_SCATTER, r.name = "count:scatter";
+  } else {
+    const int parent_bits = sbx_bits_for((uint64_t)(fsize - 1));
+    if (!CM && !r.set_bits)  // keys in ascending id order straight from the bitmap pass
+      r.keys = KEYS_FRESH, r.name = "radix:fresh";
+    else if (CM && !r.set_bits && sbx_sw().rcm_ranked_keys && (int64_t)nf * sbx_sw().rcm_ranked_div >= c.n_ranked)
+      r.keys = KEYS_FRESH_RANKED, r.name = "radix:fresh_ranked";  // ... degree-rank order from a bitmap in rank space
+    else r.low_bits = sbx_bits_for((uint64_t)(c.n - 1)), r.name = "radix:full";
+    r.np = r.keys == KEYS_FULL ? sbx_radix_plan(0, r.low_bits + parent_bits, 0, 0, r.passes)
+                               : sbx_radix_plan(0, 0, 32, 32 + parent_bits, r.passes);
+    r.sorter = SORT_RADIX;
+    if (r.np == 0) r.sorter = SORT_EMIT_ONLY, r.name = "emit_only";
+  }
+  return r;
+}
+
+// Orders the nf vertices of c.nf_list — the level behind the frontier of fsize vertices — into q_next, and leaves the
+// visited bitmap (and, with mark_frontier, the frontier bitmap and the level positions) up to date.
+template <bool CM>
+static int order_level(sbx_handle_t h, RcmCall &c, unsigned level, unsigned fsize, unsigned nf, int mark_frontier,
+                       I *q_next) {
+  const LevelRoute r = level_route<CM>(c, fsize, nf, mark_frontier);
+  const int set_bits = r.set_bits;
+  if (mark_frontier && !r.bitmap_pass) SBX_HIP(h, hipMemsetAsync(c.fbits, 0, c.bm_bytes, h->stream));
+  if (r.sorter == SORT_LDS) {
+    SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_sort_small<CM>), dim3(1), dim3(1024), (const I *)c.nf_list, nf,
+                (const unsigned *)c.ppos, c.drank, c.dorder, q_next, c.vbits, c.fbits, c.lpos, mark_frontier, c.dv);
+    return SBX_OK;
+  }
+  const int parent_bits = sbx_bits_for((uint64_t)(fsize - 1));
+  if (sbx_sw().rcm_level_paths)  // (passes: digit passes of the radix sort, or of the counting sort: 9 bits each)
+    fprintf(stderr, "[rcm level-path] sweep=%s level=%u fsize=%u nf=%u route=%s passes=%d set_bits=%d mark_frontier=%d\n",
+            CM ? "cm" : "plain", level + 1, fsize, nf, r.name,
+            r.sorter == SORT_COUNTING ? (std::max(parent_bits, 1) + 8) / 9 : r.np, set_bits, mark_frontier);
+  const unsigned g = sbx_grid_for(nf, 256, 4096);
+  uint32_t *k32 = (uint32_t *)c.ka, *v32 = k32 + c.n, *k32b = (uint32_t *)c.kb, *v32b = k32b + c.n;
+  if (r.keys == KEYS_FULL) {
+    SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_keys<CM>), dim3(g), dim3(256), (const I *)c.nf_list, nf,
+                (const unsigned *)c.ppos, c.drank, c.ka, c.dv, r.low_bits);
+  } else {
+    // bitmap words -> (scan of the blocks' totals) -> keys: 64-bit keys for the radix sort, (parent position, low
+    // field) pairs of 32 bits for the counting sort
+    const int64_t span = CM ? c.n_ranked : c.n;
+    const int64_t words = (span + 63) / 64;
+    const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
+    if (r.keys == KEYS_FRESH) {
+      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words, dim3((unsigned)fw_blocks), dim3(256), (const unsigned *)c.ppos,
+                  (unsigned long long *)c.vbits, mark_frontier ? (unsigned long long *)c.fbits : (unsigned long long *)nullptr,
+                  c.fresh64, c.wcnt, c.woff, c.n);
+    } else if (r.keys == KEYS_FRESH_RANKED) {
+      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words_ranked, dim3((unsigned)fw_blocks), dim3(256),
+                  (const unsigned *)c.ppos, (const unsigned *)c.vbits, c.dorder, c.fresh64, c.wcnt, c.woff, c.n_ranked);
+    } else {
+      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_scatter, dim3(g), dim3(256), (const I *)c.nf_list, nf,
+                  CM ? c.drank : (const uint32_t *)nullptr, c.fresh64);
+      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_counts, dim3((unsigned)fw_blocks), dim3(64),
+                  (const unsigned long long *)c.fresh64, c.wcnt, c.woff, words);
+    }
+    const int scanned = fw_blocks > RCM_FW_INLINE ? 1 : 0;
+    if (scanned) SBX_TRY(sbx_exclusive_scan_i32(h, c.woff, c.woff, fw_blocks, nullptr));
+    const bool pairs = r.sorter == SORT_COUNTING;
+    SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_keys_from_fresh, dim3((unsigned)fw_blocks), dim3(256), c.fresh64,
+                (const int *)c.wcnt, (const int *)c.woff, scanned, (const unsigned *)c.ppos,
+                CM ? c.dorder : (const uint32_t *)nullptr, pairs ? (uint64_t *)nullptr : c.ka,
+                pairs ? k32 : (uint32_t *)nullptr, pairs ? v32 : (uint32_t *)nullptr, words, c.dv);
+  }
+  if (r.sorter == SORT_COUNTING) {
+    const LevelEmit em = {CM ? c.dorder : nullptr, q_next, set_bits ? c.vbits : nullptr,
+                          (set_bits && mark_frontier) ? c.fbits : nullptr, mark_frontier ? c.lpos : nullptr};
+    SBX_TRY(sbx_cs::sort_emit(h, SBX_K_LEVEL_ORDER, k32, v32, k32b, v32b, (int64_t)nf, parent_bits, em, c.cs_scratch));
+  } else if (r.sorter == SORT_RADIX) {
+    // the last digit pass writes the queue, the bits and the level positions itself (no pass over sorted keys)
+    const sbx_radix_emit em = {CM ? c.dorder : nullptr, (uint32_t *)q_next, set_bits ? c.vbits : nullptr,
+                               (set_bits && mark_frontier) ? c.fbits : nullptr, mark_frontier ? c.lpos : nullptr,
+                               r.low_bits < 32 ? (1u << r.low_bits) - 1u : 0u};
+    SBX_TRY(sbx_radix_sort_emit(h, c.ka, c.kb, nf, r.passes, r.np, &em));
+  } else {  // one parent and keys already in id order: nothing to sort
+    SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_emit<CM>), dim3(g), dim3(256), (const uint64_t *)c.ka, nf, c.dorder,
+                q_next, c.vbits, c.fbits, c.lpos, mark_frontier, set_bits, c.dv);
+  }
+  if (CM && !set_bits)
+    SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_visited_from_ppos, dim3(sbx_grid_for(c.n, 256 * 4, 4096)), dim3(256),
+                (const unsigned *)c.ppos, (unsigned long long *)c.vbits,
+                mark_frontier ? (unsigned long long *)c.fbits : (unsigned long long *)nullptr, c.n);
+  return SBX_OK;
+}
+
 // One ordered BFS over the component containing the root (fixed_root >= 0, or the
 // device-resident dv->root).  CM selects Cuthill-McKee child order.  Direction per
 // level: top-down (frontier pushes) unless the frontier is large and owns more than
 // four times as many edges as the still-unvisited remainder — then bottom-up (pull).
 template <bool CM>
-int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, BfsResult *out, bool *spec_failed = nullptr) {
+int run_bfs(sbx_handle_t h, RcmCall &c, I fixed_root, I comp_label, BfsResult *out, bool *spec_failed = nullptr) {
   if (spec_failed) *spec_failed = false;
-  const size_t bm_bytes = (size_t)((b.n + 31) / 32) * sizeof(unsigned);
-  // vbits and fbits are adjacent pieces of one allocation (sbx_rcm_reorder): one fill clears both
+  const size_t bm_bytes = c.bm_bytes;
+  // vbits and fbits are adjacent pieces of one allocation (alloc_buffers): one fill clears both
   // (also the bitmap the level ordering scatters into: k_rank_scatter)
-  const StartClear sc = {b.vbits, (unsigned long long)((b.fbits - b.vbits) + bm_bytes / sizeof(unsigned)),
-                         (unsigned *)b.fresh64, (unsigned long long)(2 * ((b.n + 63) / 64 + 1)), nullptr, 0};
-  if (CM && b.side_stage && *b.side_stage >= 2 && !*b.side_joined) {
-    SBX_HIP(h, hipStreamWaitEvent(h->stream, b.side_event, 0));
-    *b.side_joined = true;
+  const StartClear sc = {c.vbits, (unsigned long long)((c.fbits - c.vbits) + bm_bytes / sizeof(unsigned)),
+                         (unsigned *)c.fresh64, (unsigned long long)(2 * ((c.n + 63) / 64 + 1)), nullptr, 0};
+  if (CM && c.cc_forked && c.cc_stage >= 2 && !c.cc_joined) {  // (see RcmCall::cc_forked)
+    SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[3], 0));
+    c.cc_joined = true;
   }
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_bfs_start, dim3(RCM_START_GRID), dim3(256), b.rp, b.vbits, b.fbits, b.lpos, b.ppos, b.q,
-              b.dv, fixed_root, sc);
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_bfs_start, dim3(RCM_START_GRID), dim3(256), c.rp, c.vbits, c.fbits, c.lpos, c.ppos, c.q,
+              c.dv, fixed_root, sc);
   unsigned off = 0, fsize = 1, level = 0, total = 1;
-  const unsigned max_grid = (unsigned)h->num_cus * 8;
-  // the hub kernel runs as exactly one resident wave of workgroups: a partial second wave (x8 on a kernel that
-  // fits 5 per CU) left a tail that cost 15 %
-  static int heavy_per_cu = 0;
-  if (heavy_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bfs_expand_heavy<0>, 256, 0) != hipSuccess || nb < 1) nb = 4;
-    heavy_per_cu = nb;
-  }
-  const unsigned heavy_grid = (unsigned)h->num_cus * (unsigned)heavy_per_cu;
-  int64_t remaining = b.nnz;      // adjacency entries owned by vertices not yet in any level
+  const unsigned hub_grid = heavy_grid<0>(h);
+  int64_t remaining = c.nnz;      // adjacency entries owned by vertices not yet in any level
   int64_t frontier_edges = -1;    // degree sum of the current frontier (-1: level 0, read lazily)
   bool try_small = true;  // false right after the small-level kernel declined this very frontier
   bool frontier_unmarked = false;  // the current frontier was published by the small-level kernel (no fbits/lpos)
@@ -2169,20 +2426,14 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
     bool expanded_by_small = false;
     RcmDev hd;
     if (try_small && fsize <= (unsigned)SL_MAXF) {
-      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, (k_bfs_small_levels<CM>), dim3(1), dim3(1024), b.rp, b.col, b.q, b.vbits, b.fbits,
-                  b.lpos, b.ppos, b.nf_list, b.drank, b.dorder, off, fsize, level, total, b.dv);
+      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, (k_bfs_small_levels<CM>), dim3(1), dim3(1024), c.rp, c.col, c.q, c.vbits, c.fbits,
+                  c.lpos, c.ppos, c.nf_list, c.drank, c.dorder, off, fsize, level, total, c.dv);
       SBX_LAUNCH_CHECK(h);
-      SBX_TRY(bfs_first_launch(b));
-      SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
-      if (b.tie_unverified && *b.tie_unverified) {  // (the sweep's first read-back: see BfsBuffers::tie_unverified)
-        *b.tie_unverified = false;
-        if (!hd.tie_done) {
-          if (!spec_failed) SBX_FAIL(h, SBX_ERR_INTERNAL, "run_bfs: an unverified tie-break in front of a sweep that cannot be redone");
-          *spec_failed = true;
-          return SBX_OK;
-        }
-      }
-      if (b.last_read) *b.last_read = hd, *b.last_read_joined = b.side_joined && *b.side_joined;
+      SBX_TRY(bfs_first_launch(c));
+      SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));
+      SBX_TRY(check_tie_walk(h, c, hd, spec_failed, "run_bfs"));
+      if (spec_failed && *spec_failed) return SBX_OK;
+      if (c.cc_forked) c.last_read = hd, c.last_read_joined = c.cc_joined;
       remaining -= (int64_t)hd.sl_edges;
       if (remaining < 0) remaining = 0;
       off = hd.sl_off;
@@ -2204,65 +2455,63 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
     const bool bottom_up = frontier_edges >= 0 && fsize >= 8192 && (double)frontier_edges > sbx_sw().bu_ratio * (double)remaining;
     if (bottom_up) {
       if (frontier_unmarked) {
-        SBX_HIP(h, hipMemsetAsync(b.fbits, 0, bm_bytes, h->stream));
+        SBX_HIP(h, hipMemsetAsync(c.fbits, 0, bm_bytes, h->stream));
         SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_mark_frontier, dim3(sbx_grid_for(fsize, 256, 1024)), dim3(256),
-                    (const I *)(b.q + off), fsize, b.fbits, b.lpos);
+                    (const I *)(c.q + off), fsize, c.fbits, c.lpos);
       }
       if (sbx_sw().rcm_bu_blocks)
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col,
-                    b.label, comp_label, (const unsigned *)b.vbits, (const unsigned *)b.ebits,
-                    (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), c.rp, c.col,
+                    c.label, comp_label, (const unsigned *)c.vbits, (const unsigned *)c.ebits,
+                    (const unsigned *)c.fbits, (const unsigned *)c.lpos, c.ppos, c.nf_list, c.n, c.dv, c.heavy, c.heavy_cap);
       else
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col, b.label,
-                    comp_label, (const unsigned *)b.vbits, (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos,
-                    b.nf_list, b.n, b.dv, b.heavy, b.heavy_cap);
-      if (b.max_deg > (unsigned)RCM_BU_HEAVY)
-        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_heavy, dim3(8 * (unsigned)h->num_cus), dim3(256), b.rp, b.col,
-                    (const unsigned *)b.fbits, (const unsigned *)b.lpos, b.ppos, b.nf_list, b.dv,
-                    (const uint64_t *)b.heavy, b.heavy_cap);
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), c.rp, c.col, c.label,
+                    comp_label, (const unsigned *)c.vbits, (const unsigned *)c.fbits, (const unsigned *)c.lpos, c.ppos,
+                    c.nf_list, c.n, c.dv, c.heavy, c.heavy_cap);
+      if (c.max_deg > (unsigned)RCM_BU_HEAVY)
+        SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_bfs_bottom_up_heavy, dim3(8 * (unsigned)h->num_cus), dim3(256), c.rp, c.col,
+                    (const unsigned *)c.fbits, (const unsigned *)c.lpos, c.ppos, c.nf_list, c.dv,
+                    (const uint64_t *)c.heavy, c.heavy_cap);
     } else {
-      const unsigned waves_needed = (fsize + RCM_VPW - 1) / RCM_VPW;
-      unsigned grid = (waves_needed + 3) / 4;
-      if (grid > max_grid) grid = max_grid;
-      if (grid < 1) grid = 1;
+      const unsigned grid = topdown_grid(h, fsize);
       const UnorderedSweep none = {nullptr, nullptr, nullptr, 0u};
       // A wide frontier with hubs: the light rows' kernel — tens of thousands of short dependent chains, the GPU mostly
       // idle — used to run in front of the hub kernel because it also queues the hubs' chunks.  Now a first launch only
       // queues (part 1: ~10 us), the hub kernel follows at once and the light rows (part 2) run beside it on a side
       // stream: 85 us off the widest level of the bench matrix's Cuthill-McKee sweep.
-      const bool split = b.max_deg > (unsigned)RCM_LIGHT && fsize >= 4096 && !h->prof_on && sbx_sw().rcm_split_expand && h->aux_ready;
+      const bool split = c.max_deg > (unsigned)RCM_LIGHT && fsize >= 4096 && !h->prof_on && sbx_sw().rcm_split_expand && h->aux_ready;
       if (split) {
         hipStream_t main_s = h->stream;
         const bool was_dirty = h->aux_dirty;
-        SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<0>, dim3(grid), dim3(256), b.rp, b.col, (const I *)(b.q + off),
-                    fsize, level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list, b.heavy, b.hub_dir, b.dv, none, 1);
+        SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<0>, dim3(grid), dim3(256), c.rp, c.col, (const I *)(c.q + off),
+                    fsize, level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list, c.heavy, c.hub_dir, c.dv, none, 1);
         SBX_HIP(h, hipEventRecord(h->aux_event[4], main_s));
         SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[2], h->aux_event[4], 0));
         h->aux_dirty = true;
-        h->stream = h->aux_stream[2];
-        hipLaunchKernelGGL(k_bfs_expand<0>, dim3(grid), dim3(256), 0, h->stream, b.rp, b.col, (const I *)(b.q + off), fsize,
-                           level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list, b.heavy, b.hub_dir, b.dv, none, 2);
-        const hipError_t e1 = hipGetLastError(), e2 = hipEventRecord(h->aux_event[5], h->stream);
-        h->stream = main_s;
-        if (e1 != hipSuccess || e2 != hipSuccess) SBX_FAIL(h, SBX_ERR_HIP, "run_bfs: side launch failed");
-        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<0>, dim3(heavy_grid), dim3(256), b.rp, b.col,
-                    (const I *)(b.q + off), level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list,
-                    (const uint64_t *)b.heavy, (const uint2 *)b.hub_dir, grid, b.dv, none);
+        {
+          sbx_stream_scope on_side(h, h->aux_stream[2]);
+          SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<0>, dim3(grid), dim3(256), c.rp, c.col, (const I *)(c.q + off),
+                      fsize, level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list, c.heavy, c.hub_dir, c.dv, none, 2);
+          SBX_LAUNCH_CHECK(h);
+          SBX_HIP(h, hipEventRecord(h->aux_event[5], h->stream));
+        }
+        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<0>, dim3(hub_grid), dim3(256), c.rp, c.col,
+                    (const I *)(c.q + off), level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list,
+                    (const uint64_t *)c.heavy, (const uint2 *)c.hub_dir, grid, c.dv, none);
         SBX_HIP(h, hipStreamWaitEvent(main_s, h->aux_event[5], 0));
         h->aux_dirty = was_dirty;
       } else {
-      SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<0>, dim3(grid), dim3(256), b.rp, b.col, (const I *)(b.q + off),
-                  fsize, level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list, b.heavy, b.hub_dir, b.dv, none, 0);
-      if (b.max_deg > (unsigned)RCM_LIGHT)  // mesh-like inputs have no hubs: one launch less per level
-        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<0>, dim3(heavy_grid), dim3(256), b.rp, b.col,
-                    (const I *)(b.q + off), level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list,
-                    (const uint64_t *)b.heavy, (const uint2 *)b.hub_dir, grid, b.dv, none);
+      SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<0>, dim3(grid), dim3(256), c.rp, c.col, (const I *)(c.q + off),
+                  fsize, level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list, c.heavy, c.hub_dir, c.dv, none, 0);
+      if (c.max_deg > (unsigned)RCM_LIGHT)  // mesh-like inputs have no hubs: one launch less per level
+        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<0>, dim3(hub_grid), dim3(256), c.rp, c.col,
+                    (const I *)(c.q + off), level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list,
+                    (const uint64_t *)c.heavy, (const uint2 *)c.hub_dir, grid, c.dv, none);
       }
     }
     SBX_LAUNCH_CHECK(h);
-    SBX_TRY(bfs_first_launch(b));
-    SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
-    if (b.last_read) *b.last_read = hd, *b.last_read_joined = b.side_joined && *b.side_joined;
+    SBX_TRY(bfs_first_launch(c));
+    SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));
+    if (c.cc_forked) c.last_read = hd, c.last_read_joined = c.cc_joined;
     }
     frontier_unmarked = false;
     const unsigned nf = hd.nf;
@@ -2271,121 +2520,15 @@ int run_bfs(sbx_handle_t h, const BfsBuffers &b, I fixed_root, I comp_label, Bfs
               CM ? "cm" : "plain", level, fsize, (long long)frontier_edges, (long long)remaining, nf,
               (unsigned long long)hd.fedges);
     if (nf == 0) break;
-    if (frontier_edges < 0) remaining -= (int64_t)0;  // level 0's degree is part of hd.fedges history below
-    frontier_edges = (int64_t)hd.fedges;              // degree sum of the level just discovered
+    frontier_edges = (int64_t)hd.fedges;  // degree sum of the level just discovered
     remaining -= frontier_edges;
     if (remaining < 0) remaining = 0;
-    I *q_next = b.q + off + fsize;
+    I *q_next = c.q + off + fsize;
     // direction of the NEXT expansion is already decidable: the frontier marks (bitmap +
     // level positions) are only written when it will be bottom-up
     const bool next_bottom_up = nf >= 8192 && (double)frontier_edges > sbx_sw().bu_ratio * (double)remaining;
     const int mark_frontier = next_bottom_up ? 1 : 0;
-    // levels wide enough for the bitmap pass (k_fresh_words / k_visited_from_ppos) get every word of fbits rewritten
-    const bool bitmap_pass = nf > (unsigned)RCM_LDS_SORT && (int64_t)nf >= std::max<int64_t>(RCM_REBUILD_BITS, b.n / 128);
-    if (mark_frontier && !bitmap_pass) SBX_HIP(h, hipMemsetAsync(b.fbits, 0, bm_bytes, h->stream));
-    if (nf <= RCM_LDS_SORT) {
-      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_sort_small<CM>), dim3(1), dim3(1024), (const I *)b.nf_list, nf,
-                  (const unsigned *)b.ppos, b.drank, b.dorder, q_next, b.vbits, b.fbits, b.lpos, mark_frontier, b.dv);
-    } else {
-      const unsigned g = sbx_grid_for(nf, 256, 4096);
-      // one pass over ppos (n words) against one single-bit atomic per vertex of the level
-      const int set_bits = bitmap_pass ? 0 : 1;
-      sbx_radix_pass passes[16];
-      int np;
-      int low_bits = 32;  // width of the key's low field (vertex id or degree rank); 32: the parent position starts at bit 32
-      const char *route;  // which of the seven ways orders this level (SBX_DEBUG_RCM_LEVEL_PATHS prints it)
-      if (sbx_sw().rcm_count_sort && (int64_t)nf <= RCM_COUNT_SORT_MAX) {
-        // The level's vertices in the order of their low key field — ascending degree rank (Cuthill-McKee) or id
-        // (plain) — read off a bitmap, so that only the parent positions are left to sort, stably, by the counting
-        // sort of sbx_countsort.h: three small launches per 9-bit digit.  The bitmap comes from a pass over all
-        // (ranked) vertices when the level holds a good part of them, from the level's own list otherwise.
-        const int64_t span = CM ? b.n_ranked : b.n;
-        const int64_t words = (span + 63) / 64;
-        const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
-        if (!CM && !set_bits) {
-          route = "count:fresh";
-          SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words, dim3((unsigned)fw_blocks), dim3(256), (const unsigned *)b.ppos,
-                      (unsigned long long *)b.vbits,
-                      mark_frontier ? (unsigned long long *)b.fbits : (unsigned long long *)nullptr, b.fresh64, b.wcnt,
-                      b.woff, b.n);
-        } else if (CM && (int64_t)nf * 16 >= b.n_ranked) {  // (a scattered bit costs ~16 gathered ones)
-          route = "count:fresh_ranked";
-          SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words_ranked, dim3((unsigned)fw_blocks), dim3(256),
-                      (const unsigned *)b.ppos, (const unsigned *)b.vbits, b.dorder, b.fresh64, b.wcnt, b.woff, b.n_ranked);
-        } else {
-          route = "count:scatter";
-          SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_scatter, dim3(g), dim3(256), (const I *)b.nf_list, nf,
-                      CM ? b.drank : (const uint32_t *)nullptr, b.fresh64);
-          SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_rank_counts, dim3((unsigned)fw_blocks), dim3(64),
-                      (const unsigned long long *)b.fresh64, b.wcnt, b.woff, words);
-        }
-        const int scanned = fw_blocks > RCM_FW_INLINE ? 1 : 0;
-        if (scanned) SBX_TRY(sbx_exclusive_scan_i32(h, b.woff, b.woff, fw_blocks, nullptr));
-        uint32_t *k32 = (uint32_t *)b.ka, *v32 = k32 + b.n, *k32b = (uint32_t *)b.kb, *v32b = k32b + b.n;
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_keys_from_fresh, dim3((unsigned)fw_blocks), dim3(256), b.fresh64,
-                    (const int *)b.wcnt, (const int *)b.woff, scanned, (const unsigned *)b.ppos,
-                    CM ? b.dorder : (const uint32_t *)nullptr, (uint64_t *)nullptr, k32, v32, words, b.dv);
-        const LevelEmit em = {CM ? b.dorder : nullptr, q_next, set_bits ? b.vbits : nullptr,
-                              (set_bits && mark_frontier) ? b.fbits : nullptr, mark_frontier ? b.lpos : nullptr};
-        SBX_TRY(sbx_cs::sort_emit(h, SBX_K_LEVEL_ORDER, k32, v32, k32b, v32b, (int64_t)nf,
-                                  sbx_bits_for((uint64_t)(fsize - 1)), em, b.cs_scratch));
-        np = -1;  // ordered
-      } else if (!CM && !set_bits) {
-        // keys in ascending id order straight from the bitmap pass: only the parent positions are left to sort
-        route = "radix:fresh";
-        const int64_t words = (b.n + 63) / 64;
-        const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words, dim3((unsigned)fw_blocks), dim3(256), (const unsigned *)b.ppos,
-                    (unsigned long long *)b.vbits,
-                    mark_frontier ? (unsigned long long *)b.fbits : (unsigned long long *)nullptr, b.fresh64, b.wcnt,
-                    b.woff, b.n);
-        const int scanned = fw_blocks > RCM_FW_INLINE ? 1 : 0;
-        if (scanned) SBX_TRY(sbx_exclusive_scan_i32(h, b.woff, b.woff, fw_blocks, nullptr));
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_keys_from_fresh, dim3((unsigned)fw_blocks), dim3(256),
-                    b.fresh64, (const int *)b.wcnt, (const int *)b.woff, scanned,
-                    (const unsigned *)b.ppos, (const uint32_t *)nullptr, b.ka, (uint32_t *)nullptr, (uint32_t *)nullptr, words,
-                    b.dv);
-        np = sbx_radix_plan(0, 0, 32, 32 + sbx_bits_for((uint64_t)(fsize - 1)), passes);
-      } else if (CM && !set_bits && sbx_sw().rcm_ranked_keys && (int64_t)nf * sbx_sw().rcm_ranked_div >= b.n_ranked) {
-        // keys in ascending degree-rank order from a bitmap in rank space: only the parent positions are left to sort
-        route = "radix:fresh_ranked";
-        const int64_t words = (b.n_ranked + 63) / 64;
-        const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_fresh_words_ranked, dim3((unsigned)fw_blocks), dim3(256),
-                    (const unsigned *)b.ppos, (const unsigned *)b.vbits, b.dorder, b.fresh64, b.wcnt, b.woff, b.n_ranked);
-        const int scanned = fw_blocks > RCM_FW_INLINE ? 1 : 0;
-        if (scanned) SBX_TRY(sbx_exclusive_scan_i32(h, b.woff, b.woff, fw_blocks, nullptr));
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_keys_from_fresh, dim3((unsigned)fw_blocks), dim3(256),
-                    b.fresh64, (const int *)b.wcnt, (const int *)b.woff, scanned,
-                    (const unsigned *)b.ppos, b.dorder, b.ka, (uint32_t *)nullptr, (uint32_t *)nullptr, words, b.dv);
-        np = sbx_radix_plan(0, 0, 32, 32 + sbx_bits_for((uint64_t)(fsize - 1)), passes);
-      } else {
-        route = "radix:full";
-        low_bits = sbx_bits_for((uint64_t)(b.n - 1));
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_keys<CM>), dim3(g), dim3(256), (const I *)b.nf_list, nf,
-                    (const unsigned *)b.ppos, b.drank, b.ka, b.dv, low_bits);
-        np = sbx_radix_plan(0, low_bits + sbx_bits_for((uint64_t)(fsize - 1)), 0, 0, passes);
-      }
-      if (sbx_sw().rcm_level_paths)  // (passes: digit passes of the radix sort, or of the counting sort: 9 bits each)
-        fprintf(stderr, "[rcm level-path] sweep=%s level=%u fsize=%u nf=%u route=%s passes=%d set_bits=%d mark_frontier=%d\n",
-                CM ? "cm" : "plain", level + 1, fsize, nf, np == 0 ? "emit_only" : route,
-                np < 0 ? (std::max(sbx_bits_for((uint64_t)(fsize - 1)), 1) + 8) / 9 : np, set_bits, mark_frontier);
-      if (np < 0) {
-      } else if (np > 0) {
-        // the last digit pass writes the queue, the bits and the level positions itself (no pass over sorted keys)
-        const sbx_radix_emit em = {CM ? b.dorder : nullptr, (uint32_t *)q_next, set_bits ? b.vbits : nullptr,
-                                   (set_bits && mark_frontier) ? b.fbits : nullptr, mark_frontier ? b.lpos : nullptr,
-                                   low_bits < 32 ? (1u << low_bits) - 1u : 0u};
-        SBX_TRY(sbx_radix_sort_emit(h, b.ka, b.kb, nf, passes, np, &em));
-      } else {  // one parent and keys already in id order: nothing to sort
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, (k_level_emit<CM>), dim3(g), dim3(256), (const uint64_t *)b.ka, nf, b.dorder,
-                    q_next, b.vbits, b.fbits, b.lpos, mark_frontier, set_bits, b.dv);
-      }
-      if (CM && !set_bits)
-        SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_visited_from_ppos, dim3(sbx_grid_for(b.n, 256 * 4, 4096)), dim3(256),
-                    (const unsigned *)b.ppos, (unsigned long long *)b.vbits,
-                    mark_frontier ? (unsigned long long *)b.fbits : (unsigned long long *)nullptr, b.n);
-    }
+    SBX_TRY(order_level<CM>(h, c, level, fsize, nf, mark_frontier, q_next));
     SBX_LAUNCH_CHECK(h);
     off += fsize;
     fsize = nf;
@@ -3500,6 +3643,8 @@ __global__ void k_gb_reset(RcmDev *__restrict__ dv) {
   dv->uc_mode = 0;
   dv->uc_done = 0;
 }
+// (a sweep whose first kernels left behind an unverified tie walk — RcmDev::spec_guard — is enqueued again)
+__global__ void k_clear_spec_guard(RcmDev *__restrict__ dv) { dv->spec_guard = 0; }
 
 // ---- unordered sweeps, small levels: one launch for as many consecutive levels as stay small ------------------
 // The first levels of a sweep and its last ones hold a handful of vertices: an expansion + an n-sized collection + a
@@ -3891,134 +4036,129 @@ __global__ __launch_bounds__(256) void k_check_closed(const X *__restrict__ rp, 
   }
 }
 
+// A grid barrier of a persistent kernel gave up (gb_wait: a GPU shared with another process): the device state is put
+// back, the next few calls on this handle do not try those kernels, and the caller redoes its work with the ordered ones.
+static int gb_gave_up(sbx_handle_t h, RcmCall &c) {
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), c.dv);
+  h->rcm_gb_backoff = sbx_sw().gb_backoff;
+  return SBX_OK;
+}
+
 // one unordered bottom-up level: the kernel with the block front end, or (SBX_RCM_BU_BLOCKS=0) the one with a lane per vertex
-static void launch_ubfs_bottom_up(sbx_handle_t h, const BfsBuffers &b, I comp_label, const unsigned *cur_f,
+static void launch_ubfs_bottom_up(sbx_handle_t h, RcmCall &c, I comp_label, const unsigned *cur_f,
                                   unsigned *cur_n, unsigned *dist, unsigned level, I *nf_list, int chain, const ChainInit &ci) {
   if (sbx_sw().rcm_bu_blocks)
-    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col,
-                b.label, comp_label, b.vbits, b.ebits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up_blocks, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), c.rp, c.col,
+                c.label, comp_label, c.vbits, c.ebits, cur_f, cur_n, dist, level, nf_list, c.n, c.dv, chain, ci);
   else
-    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), b.rp, b.col, b.label,
-                comp_label, b.vbits, cur_f, cur_n, dist, level, nf_list, b.n, b.dv, chain, ci);
+    SBX_KLAUNCH(h, SBX_K_BFS_BOTTOMUP, k_ubfs_bottom_up, dim3(bu_grid(h)), dim3(RCM_BU_THREADS), c.rp, c.col, c.label,
+                comp_label, c.vbits, cur_f, cur_n, dist, level, nf_list, c.n, c.dv, chain, ci);
 }
 
 // One unordered sweep from fixed_root (>= 0) or dv->root: level sets only.  *too_deep is set when the sweep passed the
 // depth limit (ub_max_levels) and was abandoned: the caller runs the ordered sweep instead.
-static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, unsigned *nbits_buf, unsigned *cone,
-                    I fixed_root, I comp_label, BfsResult *out, bool *too_deep, bool *spec_failed = nullptr) {
+static int run_ubfs(sbx_handle_t h, RcmCall &c, I fixed_root, I comp_label, BfsResult *out, bool *too_deep,
+                    bool *spec_failed = nullptr) {
   if (spec_failed) *spec_failed = false;
-  const bool claim_was_clean = *b.claim_clean;
-  const size_t bm_bytes = (size_t)((b.n + 31) / 32) * sizeof(unsigned);
-  const int64_t words = (b.n + 63) / 64;
+  const bool claim_was_clean = c.claim_clean;
+  const size_t bm_bytes = c.bm_bytes;
+  const int64_t words = (c.n + 63) / 64;
   const int64_t fw_blocks = (words + RCM_FW_WORDS - 1) / RCM_FW_WORDS;
   *too_deep = false;
+  auto abandon = [&]() -> int { return *too_deep = true, SBX_OK; };  // (the caller runs the ordered sweep instead)
   // the start kernel clears the sweep's bitmaps, the tie-break's cone bitmap (ubfs_pick_root) and — after a sweep that
   // did not run to its end — the claim bytes
-  const StartClear sc = {b.vbits, (unsigned long long)((b.fbits - b.vbits) + bm_bytes / sizeof(unsigned)),
-                         cone, (unsigned long long)(bm_bytes / sizeof(unsigned)),
-                         (unsigned *)claim8, *b.claim_clean ? 0ull : (unsigned long long)((b.n + 3) / 4)};
-  *b.claim_clean = false;  // (until this sweep has run to its end: every level's collection pass clears what it read)
-  unsigned *dist = b.lpos;  // level positions are an ordered sweep's business: the array is free here
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_start, dim3(RCM_START_GRID), dim3(256), b.rp, b.vbits, b.fbits, dist, b.q, b.dv,
+  const StartClear sc = {c.vbits, (unsigned long long)((c.fbits - c.vbits) + bm_bytes / sizeof(unsigned)),
+                         c.cone, (unsigned long long)(bm_bytes / sizeof(unsigned)),
+                         (unsigned *)c.claim8, c.claim_clean ? 0ull : (unsigned long long)((c.n + 3) / 4)};
+  c.claim_clean = false;  // (until this sweep has run to its end: every level's collection pass clears what it read)
+  unsigned *dist = c.lpos;  // level positions are an ordered sweep's business: the array is free here
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_start, dim3(RCM_START_GRID), dim3(256), c.rp, c.vbits, c.fbits, dist, c.q, c.dv,
               fixed_root, sbx_sw().gb_spins, sc);
   unsigned off = 0, fsize = 1, level = 0, total = 1;
-  const unsigned max_grid = (unsigned)h->num_cus * 8;
-  static int heavy_per_cu = 0;
-  if (heavy_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bfs_expand_heavy<1>, 256, 0) != hipSuccess || nb < 1) nb = 4;
-    heavy_per_cu = nb;
-  }
-  const unsigned heavy_grid = (unsigned)h->num_cus * (unsigned)heavy_per_cu;
-  int64_t remaining = b.nnz, frontier_edges = -1;
-  unsigned *cur_f = b.fbits, *cur_n = nbits_buf;  // frontier bitmap / the one a bottom-up level writes (swapped after it)
+  const unsigned hub_grid = heavy_grid<1>(h);
+  int64_t remaining = c.nnz, frontier_edges = -1;
+  unsigned *cur_f = c.fbits, *cur_n = c.nbits;  // frontier bitmap / the one a bottom-up level writes (swapped after it)
   bool fbits_valid = true;  // cur_f holds exactly the current frontier (the root, or what the level kernels left)
   unsigned rounds = 0;      // host round trips of this sweep
   const bool dbg_check = sbx_sw().rcm_check;
   std::vector<std::string> trace;
-  auto note = [&](const char *what, unsigned a, unsigned b_, long long c) {
+  auto note = [&](const char *what, unsigned a, unsigned b_, long long c_) {
     if (!dbg_check) return;
     char buf[160];
     snprintf(buf, sizeof buf, "%s level %u off %u fsize %u total %u fe %lld rem %lld | %u %u %lld", what, level, off, fsize, total,
-             (long long)frontier_edges, (long long)remaining, a, b_, c);
+             (long long)frontier_edges, (long long)remaining, a, b_, c_);
     trace.push_back(buf);
   };
-  while (true) {
-    if (++rounds > sbx_sw().ub_max_levels) {
-      *too_deep = true;
-      return SBX_OK;
+  // the sweep's state as a chain on the device left it (uc_advance): its last link's, or its tail small-level run's
+  enum ChainEnd { CHAIN_GO_ON, CHAIN_DONE, CHAIN_DEEP };
+  auto take_chain = [&](const RcmDev &d) -> ChainEnd {
+    if (d.uc_flips & 1u) std::swap(cur_f, cur_n);
+    rounds += d.uc_flips;
+    remaining = (int64_t)d.uc_remaining;
+    if (d.uc_small_ran) {
+      const bool moved = d.ur_level != d.uc_level;
+      off = d.ur_off, fsize = d.ur_size, level = d.ur_level, total = d.ur_total;
+      frontier_edges = (int64_t)d.ur_fe;
+      if (moved) fbits_valid = false;
+      if (d.ur_status == UR_DONE) return CHAIN_DONE;
+      // UR_STOP: a frontier for the big kernels again (the head of the loop looks at it and passes it on)
+      return d.ur_status == UR_DEEP ? CHAIN_DEEP : CHAIN_GO_ON;
     }
+    off = d.uc_off, fsize = d.uc_size, level = d.uc_level, total = d.uc_total;
+    if (d.uc_mode == UC_DONE) return CHAIN_DONE;
+    frontier_edges = (int64_t)d.uc_fe;  // UC_BU (the chain was too short) / UC_HOST (a top-down level): the loop goes on
+    return CHAIN_GO_ON;
+  };
+  while (true) {
+    if (++rounds > sbx_sw().ub_max_levels) return abandon();
     if (frontier_edges < 0 || (frontier_edges <= (int64_t)UR_MAX_E && fsize <= UR_MAX_N)) {
       // small levels: as many as stay small, in one launch
-      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                  (I *)b.heavy, b.dv, off, fsize, level, total, (long long)frontier_edges, sbx_sw().ub_max_levels, 0);
+      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), c.rp, c.col, c.vbits, dist, c.q,
+                  (I *)c.heavy, c.dv, off, fsize, level, total, (long long)frontier_edges, sbx_sw().ub_max_levels, 0);
       // At a sweep's start on a big graph this run usually ends at a frontier for the bottom-up kernels: the chain that
       // follows is enqueued now and begun on the device (k_ubfs_chain_from_small) — one read-back for the head run and the
       // chain instead of two.  Where the run ends otherwise (the sweep is over, a top-down level is due, too deep) the
-      // half-dozen launches leave at once: only where it can pay (BfsBuffers::head_chain, a graph that is not small).
+      // half-dozen launches leave at once: only where it can pay (RcmCall::head_chain, a graph that is not small).
       const int spec_len =
-          (sbx_sw().rcm_head_chain && b.head_chain && frontier_edges < 0 && b.n >= ((int64_t)1 << 17)) ? sbx_sw().rcm_ubfs_chain : 0;
+          (sbx_sw().rcm_head_chain && c.head_chain && frontier_edges < 0 && c.n >= ((int64_t)1 << 17)) ? sbx_sw().rcm_ubfs_chain : 0;
       if (spec_len > 0) {
         const ChainInit ci0 = {0u, 0u, 0u, 0u, 0ll, UBU_RATIO};
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_from_small, dim3(1), dim3(1), b.dv, (long long)remaining, UBU_RATIO,
+        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_from_small, dim3(1), dim3(1), c.dv, (long long)remaining, UBU_RATIO,
                     level);
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
-                    (const unsigned *)b.vbits, (const unsigned *)dist, 0u, b.n, cur_f, (const RcmDev *)b.dv);
+        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(c.n, 256, 4096)), dim3(256),
+                    (const unsigned *)c.vbits, (const unsigned *)dist, 0u, c.n, cur_f, (const RcmDev *)c.dv);
         unsigned *cf = cur_f, *cn = cur_n;
         for (int i = 0; i <= spec_len; i++) {
-          launch_ubfs_bottom_up(h, b, comp_label, cf, cn, dist, 0u, b.q, 1, ci0);
+          launch_ubfs_bottom_up(h, c, comp_label, cf, cn, dist, 0u, c.q, 1, ci0);
           std::swap(cf, cn);
         }
-        SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                    (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
+        SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), c.rp, c.col, c.vbits, dist, c.q,
+                    (I *)c.heavy, c.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
       }
       SBX_LAUNCH_CHECK(h);
       // (the hook's work needs the degree counts: while this read-back is the one that delivers them it waits for the
       // next launch with a long cover)
-      SBX_TRY(bfs_first_launch(b, spec_len > 0 && (!b.late_counts || *b.late_counts_ready) ? 150 : 40));
+      SBX_TRY(bfs_first_launch(c, spec_len > 0 && c.counts_ready ? 150 : 40));
       RcmDev hs;
-      SBX_TRY(sbx_readback(h, &hs, b.dv, sizeof(RcmDev)));
-      if (b.tie_unverified && *b.tie_unverified) {  // (the sweep's first read-back: see BfsBuffers::tie_unverified)
-        *b.tie_unverified = false;
-        if (!hs.tie_done) {
-          if (!spec_failed) SBX_FAIL(h, SBX_ERR_INTERNAL, "run_ubfs: an unverified tie-break in front of a sweep that cannot be redone");
-          *b.claim_clean = claim_was_clean;  // (the start kernel left before it cleared anything)
-          *spec_failed = true;
-          return SBX_OK;
-        }
-      }
-      if (b.late_counts && !*b.late_counts_ready) {
-        *b.late_counts = hs;
-        *b.late_counts_ready = true;
-      }
-      if (hs.gb_abort) {  // a grid barrier gave up (gb_wait): this sweep is redone by the ordered kernels
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-        h->rcm_gb_backoff = sbx_sw().gb_backoff;
-        *too_deep = true;
+      SBX_TRY(sbx_readback(h, &hs, c.dv, sizeof(RcmDev)));
+      SBX_TRY(check_tie_walk(h, c, hs, spec_failed, "run_ubfs"));
+      if (spec_failed && *spec_failed) {
+        c.claim_clean = claim_was_clean;  // (the start kernel left before it cleared anything)
         return SBX_OK;
+      }
+      if (!c.counts_ready) c.take_counts(hs);  // (the call's first read-back: see RcmCall::lazy_counts)
+      if (hs.gb_abort) {  // a grid barrier gave up (gb_wait): this sweep is redone by the ordered kernels
+        SBX_TRY(gb_gave_up(h, c));
+        return abandon();
       }
       if (spec_len > 0 && hs.uc_head) {
         // the head run stopped at a big frontier and the chain went on from there: as behind a chain the host launched
         note("small_run(head) + chain", hs.uc_flips, hs.uc_mode, (long long)hs.uc_remaining);
-        if (hs.uc_flips & 1u) std::swap(cur_f, cur_n);
-        rounds += hs.uc_flips;
-        remaining = (int64_t)hs.uc_remaining;
         fbits_valid = hs.uc_flips > 0;  // (no link ran: the frontier is the head run's, its bitmap was not built)
-        if (hs.uc_small_ran) {
-          const bool moved2 = hs.ur_level != hs.uc_level;
-          off = hs.ur_off, fsize = hs.ur_size, level = hs.ur_level, total = hs.ur_total;
-          frontier_edges = (int64_t)hs.ur_fe;
-          if (moved2) fbits_valid = false;
-          if (hs.ur_status == UR_DONE) break;
-          if (hs.ur_status == UR_DEEP) {
-            *too_deep = true;
-            return SBX_OK;
-          }
-          continue;
-        }
-        off = hs.uc_off, fsize = hs.uc_size, level = hs.uc_level, total = hs.uc_total;
-        if (hs.uc_mode == UC_DONE) break;
-        frontier_edges = (int64_t)hs.uc_fe;
+        const ChainEnd end = take_chain(hs);
+        if (end == CHAIN_DONE) break;
+        if (end == CHAIN_DEEP) return abandon();
         continue;
       }
       const bool moved = hs.ur_level != level;
@@ -4029,40 +4169,34 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
       frontier_edges = (int64_t)hs.ur_fe;
       if (moved) fbits_valid = false;
       if (hs.ur_status == UR_DONE) break;
-      if (hs.ur_status == UR_DEEP) {
-        *too_deep = true;
-        return SBX_OK;
-      }
+      if (hs.ur_status == UR_DEEP) return abandon();
       if (moved) continue;  // (UR_STOP with a new frontier: it is looked at again, and is big)
       // UR_STOP right at the entry: the frontier handed in was too big — expand it with the kernels below
     }
-    I *q_next = b.q + off + fsize;  // the next level is appended to the queue
-    const UnorderedSweep us = {claim8, nullptr, dist, level + 1};
+    I *q_next = c.q + off + fsize;  // the next level is appended to the queue
+    const UnorderedSweep us = {c.claim8, nullptr, dist, level + 1};
     const bool bottom_up = frontier_edges >= 0 && fsize >= 1024 && (double)frontier_edges > UBU_RATIO * (double)remaining;
     note(bottom_up ? "bottom-up" : "top-down", fbits_valid, 0, 0);
     const int chain_len = sbx_sw().rcm_ubfs_chain;
     const ChainInit ci = {off, fsize, level, total, (long long)remaining, UBU_RATIO};
     if (bottom_up) {
       if (!fbits_valid)
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(b.n, 256, 4096)), dim3(256),
-                    (const unsigned *)b.vbits, (const unsigned *)dist, level, b.n, cur_f, (const RcmDev *)nullptr);
+        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_fbits_from_dist, dim3(sbx_grid_for(c.n, 256, 4096)), dim3(256),
+                    (const unsigned *)c.vbits, (const unsigned *)dist, level, c.n, cur_f, (const RcmDev *)nullptr);
       // publishes the level itself (bitmaps, distances, queue): no collection pass
-      launch_ubfs_bottom_up(h, b, comp_label, cur_f, cur_n, dist, level + 1, q_next, chain_len > 0 ? 2 : 0, ci);
+      launch_ubfs_bottom_up(h, c, comp_label, cur_f, cur_n, dist, level + 1, q_next, chain_len > 0 ? 2 : 0, ci);
       std::swap(cur_f, cur_n);
     } else {
-      const unsigned waves_needed = (fsize + RCM_VPW - 1) / RCM_VPW;
-      unsigned grid = (waves_needed + 3) / 4;
-      if (grid > max_grid) grid = max_grid;
-      if (grid < 1) grid = 1;
-      SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<1>, dim3(grid), dim3(256), b.rp, b.col, (const I *)(b.q + off),
-                  fsize, level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list, b.heavy, b.hub_dir, b.dv, us, 0);
-      if ((b.late_counts ? b.late_counts->max_deg : b.max_deg) > (unsigned)RCM_LIGHT)
-        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<1>, dim3(heavy_grid), dim3(256), b.rp, b.col,
-                    (const I *)(b.q + off), level + 1, (const unsigned *)b.vbits, b.ppos, b.nf_list,
-                    (const uint64_t *)b.heavy, (const uint2 *)b.hub_dir, grid, b.dv, us);
-      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_ubfs_collect, dim3((unsigned)fw_blocks), dim3(256), claim8,
-                  (unsigned long long *)b.vbits, (unsigned long long *)cur_f, dist, level + 1, b.rp, q_next, b.n, b.dv);
-      if (chain_len > 0) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_next, dim3(1), dim3(1), b.dv, ci);
+      const unsigned grid = topdown_grid(h, fsize);
+      SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<1>, dim3(grid), dim3(256), c.rp, c.col, (const I *)(c.q + off),
+                  fsize, level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list, c.heavy, c.hub_dir, c.dv, us, 0);
+      if (c.max_deg > (unsigned)RCM_LIGHT)
+        SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<1>, dim3(hub_grid), dim3(256), c.rp, c.col,
+                    (const I *)(c.q + off), level + 1, (const unsigned *)c.vbits, c.ppos, c.nf_list,
+                    (const uint64_t *)c.heavy, (const uint2 *)c.hub_dir, grid, c.dv, us);
+      SBX_KLAUNCH(h, SBX_K_LEVEL_ORDER, k_ubfs_collect, dim3((unsigned)fw_blocks), dim3(256), c.claim8,
+                  (unsigned long long *)c.vbits, (unsigned long long *)cur_f, dist, level + 1, c.rp, q_next, c.n, c.dv);
+      if (chain_len > 0) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_chain_next, dim3(1), dim3(1), c.dv, ci);
     }
     SBX_LAUNCH_CHECK(h);
     fbits_valid = true;
@@ -4074,43 +4208,26 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
       // A sweep of the bench matrix: a small run, three bottom-up levels, a small run — five round trips, now two.
       unsigned *cf = cur_f, *cn = cur_n;
       for (int i = 0; i < chain_len; i++) {
-        launch_ubfs_bottom_up(h, b, comp_label, cf, cn, dist, 0u, b.q, 1, ci);
+        launch_ubfs_bottom_up(h, c, comp_label, cf, cn, dist, 0u, c.q, 1, ci);
         std::swap(cf, cn);
       }
-      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), b.rp, b.col, b.vbits, dist, b.q,
-                  (I *)b.heavy, b.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
+      SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_small_run, dim3(UR_GRID), dim3(256), c.rp, c.col, c.vbits, dist, c.q,
+                  (I *)c.heavy, c.dv, 0u, 0u, 0u, 0u, 0ll, sbx_sw().ub_max_levels, sbx_sw().chain_tail_abort ? 2 : 1);
       SBX_LAUNCH_CHECK(h);
-      SBX_TRY(bfs_first_launch(b, 150));  // (a chain of big levels is in flight: the host has nothing else to do)
-      SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
+      SBX_TRY(bfs_first_launch(c, 150));  // (a chain of big levels is in flight: the host has nothing else to do)
+      SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));
       if (hd.gb_abort) {
         // a grid barrier of the chain's small-level kernel gave up — before it could say that it ran at all: the sweep
         // is redone by the ordered kernels, as after the small-level kernel at the head of the loop
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-        h->rcm_gb_backoff = sbx_sw().gb_backoff;
-        *too_deep = true;
-        return SBX_OK;
+        SBX_TRY(gb_gave_up(h, c));
+        return abandon();
       }
-      if (hd.uc_flips & 1u) std::swap(cur_f, cur_n);
-      rounds += hd.uc_flips;
-      remaining = (int64_t)hd.uc_remaining;
-      if (hd.uc_small_ran) {  // as after the small-level kernel at the head of the loop
-        const bool moved = hd.ur_level != hd.uc_level;
-        off = hd.ur_off, fsize = hd.ur_size, level = hd.ur_level, total = hd.ur_total;
-        frontier_edges = (int64_t)hd.ur_fe;
-        if (moved) fbits_valid = false;
-        if (hd.ur_status == UR_DONE) break;
-        if (hd.ur_status == UR_DEEP) {
-          *too_deep = true;
-          return SBX_OK;
-        }
-        continue;  // UR_STOP: a frontier for the big kernels again (the head of the loop looks at it and passes it on)
-      }
-      off = hd.uc_off, fsize = hd.uc_size, level = hd.uc_level, total = hd.uc_total;
-      if (hd.uc_mode == UC_DONE) break;
-      frontier_edges = (int64_t)hd.uc_fe;  // UC_BU (the chain was too short) / UC_HOST (a top-down level): the loop goes on
+      const ChainEnd end = take_chain(hd);
+      if (end == CHAIN_DONE) break;
+      if (end == CHAIN_DEEP) return abandon();
       continue;
     }
-    SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
+    SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));
     const unsigned nf = hd.unf[(level + 1) & 1];
     note("  -> built", nf, 0, (long long)hd.ufedges[(level + 1) & 1]);
     if (nf == 0) break;
@@ -4122,13 +4239,13 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
     total += nf;
     level++;
   }
-  *b.claim_clean = true;
+  c.claim_clean = true;
   if (dbg_check) {
     unsigned *chk = nullptr;
     SBX_TRY(sbx_salloc(h, 32, &chk));
     SBX_HIP(h, hipMemsetAsync(chk, 0, 32 * sizeof(unsigned), h->stream));
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_check_closed, dim3(1024), dim3(256), b.rp, b.col, (const unsigned *)b.vbits,
-                (const unsigned *)dist, b.n, chk);
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_check_closed, dim3(1024), dim3(256), c.rp, c.col, (const unsigned *)c.vbits,
+                (const unsigned *)dist, c.n, chk);
     unsigned hc[32];
     SBX_TRY(sbx_readback(h, hc, chk, sizeof(hc)));
     if (hc[0]) {
@@ -4145,18 +4262,79 @@ static int run_ubfs(sbx_handle_t h, const BfsBuffers &b, unsigned char *claim8, 
   return SBX_OK;
 }
 
+// the tie-break by the persistent cone kernels, behind the kernels that found and marked the candidates (clear_guard: ...
+// and behind a next sweep whose first kernels left: RcmDev::spec_guard)
+static int ubfs_pick_root_slow(sbx_handle_t h, RcmCall &c, const BfsResult &r, bool *aborted, bool clear_guard) {
+  *aborted = false;
+  I *list = c.nf_list;
+  if (clear_guard) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_clear_spec_guard, dim3(1), dim3(1), c.dv);
+  SBX_LAUNCH_CHECK(h);
+  RcmDev hd;
+  if (r.last_size > UB_TIES_SMALL) {
+    // (the one-workgroup kernel of the small case names a single candidate itself: no round trip for the count)
+    SBX_TRY(bfs_first_launch(c, 20));
+    SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));
+    if (hd.nf <= 1) {
+      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_root_from_single_tie, dim3(1), dim3(1), c.dv);
+      SBX_LAUNCH_CHECK(h);
+      return SBX_OK;
+    }
+  }
+  // T_{k-1} = the level-(k-1) neighbours of T_k: the expansion kernel in cone mode appends them to the same list (its
+  // counter keeps growing); the hub kernel only runs for a level that queued hub chunks
+  const unsigned max_grid = (unsigned)h->num_cus * 8;
+  const unsigned hub_grid = heavy_grid<2>(h);
+  // Small lists — most of them — are walked by the persistent kernel, several levels per launch; a level whose list is
+  // too long for it goes through the expansion kernels in their cone mode (the range of the list stays on the device).
+  if (r.last_size > UB_TIES_SMALL) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_cone_next, dim3(1), dim3(1), c.dv, 1);
+  const unsigned cone_grid = max_grid < 512u ? max_grid : 512u;
+  for (unsigned k = r.levels - 1; k >= 2;) {  // level 0 is the root: every T_1 member hangs under it
+    SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_cone_run, dim3(UR_GRID), dim3(256), c.rp, c.col, (const unsigned *)c.vbits,
+                (const unsigned *)c.lpos, c.cone, list, (I *)c.heavy, c.dv, k);
+    // the walk down the cone goes out behind it at once: it runs if the cone is finished (the usual end of this loop) and
+    // leaves otherwise — one round trip for both instead of one each
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_descend_all, dim3(UB_DESC_GRID), dim3(256), c.rp, c.col,
+                (const unsigned *)c.vbits, (const unsigned *)c.lpos, (const unsigned *)c.cone, r.levels, c.dv, 1);
+    SBX_LAUNCH_CHECK(h);
+    SBX_TRY(bfs_first_launch(c, 40));
+    SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
+    if (hd.gb_abort) {
+      SBX_TRY(gb_gave_up(h, c));
+      *aborted = true;
+      return SBX_OK;
+    }
+    if (hd.cone_status == UR_DONE || hd.unsym) return SBX_OK;
+    k = hd.cone_k;  // its list is long: one level with the big kernels, then the persistent one again
+    const UnorderedSweep us = {nullptr, c.cone, c.lpos, k - 1};
+    SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<2>, dim3(cone_grid), dim3(256), c.rp, c.col, (const I *)list, 0u, k,
+                (const unsigned *)c.vbits, c.ppos, list, c.heavy, c.hub_dir, c.dv, us, 0);
+    if (c.max_deg > (unsigned)RCM_LIGHT)
+      SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<2>, dim3(hub_grid), dim3(256), c.rp, c.col, (const I *)list, k,
+                  (const unsigned *)c.vbits, c.ppos, list, (const uint64_t *)c.heavy, (const uint2 *)c.hub_dir, cone_grid,
+                  c.dv, us);
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_cone_next, dim3(1), dim3(1), c.dv, 0);
+    k--;
+  }
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_descend_all, dim3(UB_DESC_GRID), dim3(256), c.rp, c.col,
+              (const unsigned *)c.vbits, (const unsigned *)c.lpos, (const unsigned *)c.cone, r.levels, c.dv, 0);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(bfs_first_launch(c, 40));
+  SBX_TRY(sbx_readback(h, &hd, c.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
+  if (hd.gb_abort) {
+    SBX_TRY(gb_gave_up(h, c));
+    *aborted = true;
+  }
+  return SBX_OK;
+}
+
 // the next candidate root after an unordered sweep: first vertex in queue order among the deepest level's vertices of
 // smallest degree (see the comment above k_ubfs_start); left in dv->root
-__global__ void k_clear_spec_guard(RcmDev *__restrict__ dv) { dv->spec_guard = 0; }
-static int ubfs_pick_root_slow(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, const BfsResult &r, bool *aborted,
-                               bool clear_guard);
 // allow_unverified: the caller's next sweep can be redone (run_ubfs / run_bfs with spec_failed): a tie walk is then left
-// unverified (*b.tie_unverified) and the next sweep is enqueued straight behind it
-static int ubfs_pick_root(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, const BfsResult &r, bool *aborted,
-                          bool allow_unverified) {
+// unverified (RcmCall::tie_unverified) and the next sweep is enqueued straight behind it
+static int ubfs_pick_root(sbx_handle_t h, RcmCall &c, const BfsResult &r, bool *aborted, bool allow_unverified) {
   *aborted = false;
-  const I *last = b.q + r.last_offset;
-  I *list = b.nf_list;  // free during an unordered sweep: the marked vertices, level after level, one growing list
+  const I *last = c.q + r.last_offset;
+  I *list = c.nf_list;  // free during an unordered sweep: the marked vertices, level after level, one growing list
   // (the cone bitmap was cleared by the sweep's start kernel)
   if (r.last_size <= UB_TIES_SMALL) {
     // (the candidates' workgroup goes on to the whole tie-break where the cone is small: tie_walk; the two kernels behind
@@ -4164,22 +4342,22 @@ static int ubfs_pick_root(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, c
     TieWalkState *tw = nullptr;
     SBX_TRY(sbx_salloc(h, 1, &tw));
     const bool tw_dbg = sbx_sw().tie_walk_debug;
-    const bool spec = allow_unverified && sbx_sw().rcm_tie_walk && sbx_sw().rcm_tie_spec && !tw_dbg && b.tie_unverified;
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_ties_small, dim3(1), dim3(1024), b.rp, last, r.last_size, cone, list, b.dv, b.col,
-                (const unsigned *)b.vbits, (const unsigned *)b.lpos, sbx_sw().rcm_tie_walk ? r.levels : 0u, sbx_sw().tie_edges,
+    const bool spec = allow_unverified && sbx_sw().rcm_tie_walk && sbx_sw().rcm_tie_spec && !tw_dbg;
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_ties_small, dim3(1), dim3(1024), c.rp, last, r.last_size, c.cone, list, c.dv, c.col,
+                (const unsigned *)c.vbits, (const unsigned *)c.lpos, sbx_sw().rcm_tie_walk ? r.levels : 0u, sbx_sw().tie_edges,
                 sbx_sw().tie_cap, sbx_sw().tie_single, tw, spec ? 1u : 0u);
     if (sbx_sw().rcm_tie_walk) {
-      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_min, dim3((unsigned)h->num_cus), dim3(256), b.rp, b.col,
-                  (const unsigned *)b.vbits, (const unsigned *)b.lpos, (const I *)list, tw);
-      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_adj, dim3((unsigned)h->num_cus), dim3(256), b.rp, b.col, (const I *)list, tw);
-      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_walk_resume, dim3(1), dim3(1024), b.rp, b.col, (const unsigned *)b.vbits,
-                  (const unsigned *)b.lpos, list, b.dv, tw, sbx_sw().tie_edges, sbx_sw().tie_cap, sbx_sw().tie_single);
+      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_min, dim3((unsigned)h->num_cus), dim3(256), c.rp, c.col,
+                  (const unsigned *)c.vbits, (const unsigned *)c.lpos, (const I *)list, tw);
+      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_heavy_adj, dim3((unsigned)h->num_cus), dim3(256), c.rp, c.col, (const I *)list, tw);
+      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_tie_walk_resume, dim3(1), dim3(1024), c.rp, c.col, (const unsigned *)c.vbits,
+                  (const unsigned *)c.lpos, list, c.dv, tw, sbx_sw().tie_edges, sbx_sw().tie_cap, sbx_sw().tie_single);
       // Usually that was the whole tie-break — so the next sweep goes out behind it unseen: its first kernels leave if the
       // walk did (RcmDev::spec_guard), its first read-back tells, and the caller then comes back for the persistent
       // kernels (ubfs_pick_root_slow).  One round trip per tie-break saved.
       SBX_LAUNCH_CHECK(h);
       if (spec) {
-        *b.tie_unverified = true;
+        c.tie_unverified = true;
         return SBX_OK;
       }
       // Otherwise the host looks before it enqueues the persistent kernels (a round trip more where the walk left — rare —
@@ -4188,7 +4366,7 @@ static int ubfs_pick_root(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, c
       // components' labelling, a dozen launches — would hold the read-back up with the caller's stream idle; the next
       // sweep's first launch takes the hook along behind a whole chain of levels)
       RcmDev hw;
-      SBX_TRY(sbx_readback(h, &hw, b.dv, sizeof(RcmDev)));
+      SBX_TRY(sbx_readback(h, &hw, c.dv, sizeof(RcmDev)));
       if (tw_dbg)  // (exits: see TW_LEAVE in tie_walk; 0: it named the root)
         fprintf(stderr, "[rcm tie walk] levels %u, candidates %u: exit %u at level %u (%u)\n", r.levels, hw.tie_count,
                 hw.tie_walk_exit & 0xFFu, hw.tie_walk_exit >> 8, hw.tie_walk_arg);
@@ -4196,84 +4374,11 @@ static int ubfs_pick_root(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, c
     }
   } else {
     const unsigned g = sbx_grid_for(r.last_size, 256, 1024);
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_ties_init, dim3(1), dim3(1), b.dv);
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_min_degree, dim3(g), dim3(256), b.rp, last, r.last_size, b.dv);
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_mark_ties, dim3(g), dim3(256), b.rp, last, r.last_size, cone, list, b.dv);
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_ties_init, dim3(1), dim3(1), c.dv);
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_min_degree, dim3(g), dim3(256), c.rp, last, r.last_size, c.dv);
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_mark_ties, dim3(g), dim3(256), c.rp, last, r.last_size, c.cone, list, c.dv);
   }
-  return ubfs_pick_root_slow(h, b, cone, r, aborted, false);
-}
-// the tie-break by the persistent cone kernels, behind the kernels that found and marked the candidates (clear_guard: ...
-// and behind a next sweep whose first kernels left: RcmDev::spec_guard)
-static int ubfs_pick_root_slow(sbx_handle_t h, const BfsBuffers &b, unsigned *cone, const BfsResult &r, bool *aborted,
-                               bool clear_guard) {
-  *aborted = false;
-  I *list = b.nf_list;
-  if (clear_guard) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_clear_spec_guard, dim3(1), dim3(1), b.dv);
-  SBX_LAUNCH_CHECK(h);
-  RcmDev hd;
-  if (r.last_size > UB_TIES_SMALL) {
-    // (the one-workgroup kernel of the small case names a single candidate itself: no round trip for the count)
-    SBX_TRY(bfs_first_launch(b, 20));
-    SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));
-    if (hd.nf <= 1) {
-      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_root_from_single_tie, dim3(1), dim3(1), b.dv);
-      SBX_LAUNCH_CHECK(h);
-      return SBX_OK;
-    }
-  }
-  // T_{k-1} = the level-(k-1) neighbours of T_k: the expansion kernel in cone mode appends them to the same list (its
-  // counter keeps growing); the hub kernel only runs for a level that queued hub chunks
-  const unsigned max_grid = (unsigned)h->num_cus * 8;
-  static int heavy_per_cu = 0;
-  if (heavy_per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bfs_expand_heavy<2>, 256, 0) != hipSuccess || nb < 1) nb = 4;
-    heavy_per_cu = nb;
-  }
-  const unsigned heavy_grid = (unsigned)h->num_cus * (unsigned)heavy_per_cu;
-  // Small lists — most of them — are walked by the persistent kernel, several levels per launch; a level whose list is
-  // too long for it goes through the expansion kernels in their cone mode (the range of the list stays on the device).
-  if (r.last_size > UB_TIES_SMALL) SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_cone_next, dim3(1), dim3(1), b.dv, 1);
-  const unsigned cone_grid = max_grid < 512u ? max_grid : 512u;
-  for (unsigned k = r.levels - 1; k >= 2;) {  // level 0 is the root: every T_1 member hangs under it
-    SBX_KLAUNCH(h, SBX_K_BFS_SMALL, k_ubfs_cone_run, dim3(UR_GRID), dim3(256), b.rp, b.col, (const unsigned *)b.vbits,
-                (const unsigned *)b.lpos, cone, list, (I *)b.heavy, b.dv, k);
-    // the walk down the cone goes out behind it at once: it runs if the cone is finished (the usual end of this loop) and
-    // leaves otherwise — one round trip for both instead of one each
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_descend_all, dim3(UB_DESC_GRID), dim3(256), b.rp, b.col,
-                (const unsigned *)b.vbits, (const unsigned *)b.lpos, (const unsigned *)cone, r.levels, b.dv, 1);
-    SBX_LAUNCH_CHECK(h);
-    SBX_TRY(bfs_first_launch(b, 40));
-    SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
-    if (hd.gb_abort) {
-      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-      h->rcm_gb_backoff = sbx_sw().gb_backoff;
-      *aborted = true;
-      return SBX_OK;
-    }
-    if (hd.cone_status == UR_DONE || hd.unsym) return SBX_OK;
-    k = hd.cone_k;  // its list is long: one level with the big kernels, then the persistent one again
-    const UnorderedSweep us = {nullptr, cone, b.lpos, k - 1};
-    SBX_KLAUNCH(h, SBX_K_BFS_EXPAND, k_bfs_expand<2>, dim3(cone_grid), dim3(256), b.rp, b.col, (const I *)list, 0u, k,
-                (const unsigned *)b.vbits, b.ppos, list, b.heavy, b.hub_dir, b.dv, us, 0);
-    if (b.max_deg > (unsigned)RCM_LIGHT)
-      SBX_KLAUNCH(h, SBX_K_BFS_HEAVY, k_bfs_expand_heavy<2>, dim3(heavy_grid), dim3(256), b.rp, b.col, (const I *)list, k,
-                  (const unsigned *)b.vbits, b.ppos, list, (const uint64_t *)b.heavy, (const uint2 *)b.hub_dir, cone_grid,
-                  b.dv, us);
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_cone_next, dim3(1), dim3(1), b.dv, 0);
-    k--;
-  }
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_ubfs_descend_all, dim3(UB_DESC_GRID), dim3(256), b.rp, b.col,
-              (const unsigned *)b.vbits, (const unsigned *)b.lpos, (const unsigned *)cone, r.levels, b.dv, 0);
-  SBX_LAUNCH_CHECK(h);
-  SBX_TRY(bfs_first_launch(b, 40));
-  SBX_TRY(sbx_readback(h, &hd, b.dv, sizeof(RcmDev)));  // (the walk must be known to have finished: see gb_wait)
-  if (hd.gb_abort) {
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_gb_reset, dim3(1), dim3(1), b.dv);
-    h->rcm_gb_backoff = sbx_sw().gb_backoff;
-    *aborted = true;
-  }
-  return SBX_OK;
+  return ubfs_pick_root_slow(h, c, r, aborted, false);
 }
 
 // parent positions back to UNSEEN after a sweep: per reached vertex, or — when the sweep reached a good part of
@@ -4284,6 +4389,418 @@ static int reset_ppos(sbx_handle_t h, const I *q, unsigned count, unsigned *ppos
   } else {
     SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_reset_visited, dim3(sbx_grid_for(count, 256, 4096)), dim3(256), q, count, ppos);
     SBX_LAUNCH_CHECK(h);
+  }
+  return SBX_OK;
+}
+
+// the next candidate root after an ordered sweep: the deepest level's first vertex of smallest degree, left in dv->root
+static int pick_root_ordered(sbx_handle_t h, RcmCall &c, const BfsResult &r) {
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_pick_root, dim3(sbx_grid_for(r.last_size, 256, 1024)), dim3(256), c.rp,
+              (const I *)(c.q + r.last_offset), r.last_size, c.dv);
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_set_root_from_best, dim3(1), dim3(1), (const I *)(c.q + r.last_offset), c.dv);
+  return SBX_OK;
+}
+
+// a grid barrier of the tie-break gave up: the same sweep again, ordered (dv->root still is its root) + its root pick
+static int redo_sweep_ordered(sbx_handle_t h, RcmCall &c, I comp_label, BfsResult *r) {
+  SBX_TRY(run_bfs<false>(h, c, -1, comp_label, r));
+  return pick_root_ordered(h, c, *r);
+}
+
+// (a sweep behind an unverified tie walk comes back at once when the walk had left: the persistent kernels then finish
+// the tie-break on the sweep r still describes — exactly what followed the tie-break before — and the sweep is enqueued
+// again)
+static int settle_tie(sbx_handle_t h, RcmCall &c, I comp_label, BfsResult *r, bool *deep) {
+  bool aborted = false;
+  SBX_TRY(ubfs_pick_root_slow(h, c, *r, &aborted, true));
+  if (aborted) {
+    *deep = true;
+    SBX_TRY(redo_sweep_ordered(h, c, comp_label, r));
+    SBX_TRY(reset_ppos(h, (const I *)c.q, r->count, c.ppos, c.n));
+  }
+  return SBX_OK;
+}
+
+// Pseudo-peripheral search and Cuthill-McKee sweep of one host-ordered component (root = its smallest vertex): leaves
+// the component's order in q.  have_first_sweep: the call's first sweep (c.r0) was exactly this component's first sweep.
+//
+// pseudo-peripheral search from the component's smallest vertex (:22-81)
+//
+// The search ends with the first candidate root whose sweep does not deepen the level
+// structure, and the Cuthill-McKee sweep that follows starts from that same vertex: the
+// two sweeps discover identical levels and differ only in the order inside a level.  So
+// from the third candidate on (the usual place for the search to end) the Cuthill-McKee
+// sweep is run FIRST.  If the structure did not deepen it already is the final sweep —
+// one sweep saved; if it did, the plain sweep is still needed (its order inside the last
+// level breaks the ties for the next candidate) and the speculative one was wasted.
+// Either way the output is the reference's; only the number of sweeps differs.
+static int search_component(sbx_handle_t h, RcmCall &c, I root, I size, bool have_first_sweep, Searched &out) {
+  out = Searched{};
+  BfsResult &r = out.r;
+  int64_t prev_ecc = -1, ecc = 0;
+  I fixed = root;
+  bool deep = !c.unordered_ok;  // a sweep of more than UB_MAX_LEVELS levels: this component keeps ordered sweeps
+  while (prev_ecc != ecc) {
+    prev_ecc = ecc;
+    bool unordered = false;  // the sweep just run kept no order inside its levels
+    if (have_first_sweep) {
+      r = c.r0;
+      have_first_sweep = false;
+      unordered = c.r0_unordered;
+      if (!unordered) deep = true;
+    } else {
+      if (out.candidate >= RCM_SPECULATE_FROM) {
+        SBX_TRY(c.join_ranks());
+        bool sf = false;
+        SBX_TRY(run_bfs<true>(h, c, fixed, root, &r, &sf));
+        if (sf) {
+          SBX_TRY(settle_tie(h, c, root, &r, &deep));
+          SBX_TRY(run_bfs<true>(h, c, (I)-1, root, &r));
+        }
+        out.sweeps++;
+        out.levels += r.levels;
+        const int64_t e = (int64_t)r.levels - 1;
+        const int64_t deepest = e > ecc ? e : ecc;
+        if (deepest == ecc || (int64_t)r.count == deepest + 1) {
+          out.cm_done = true;  // this candidate is the root and q already holds its Cuthill-McKee order
+          break;
+        }
+        SBX_TRY(reset_ppos(h, (const I *)c.q, r.count, c.ppos, c.n));
+        fixed = -1;  // k_bfs_start left the root on the device
+      }
+      if (!deep) {
+        bool sf = false;
+        SBX_TRY(run_ubfs(h, c, fixed, root, &r, &deep, &sf));
+        if (sf) {
+          SBX_TRY(settle_tie(h, c, root, &r, &deep));
+          if (!deep) SBX_TRY(run_ubfs(h, c, (I)-1, root, &r, &deep));
+        }
+        unordered = !deep;
+        c.unordered_sweeps += unordered;
+      }
+      if (deep) SBX_TRY(run_bfs<false>(h, c, fixed, root, &r));
+    }
+    fixed = -1;  // later sweeps start from the device-resident root
+    out.candidate++;
+    out.sweeps++;
+    out.levels += r.levels;
+    const int64_t e = (int64_t)r.levels - 1;
+    if (e > ecc) ecc = e;
+    const bool path = (int64_t)r.count == ecc + 1;
+    if (!path && prev_ecc != ecc) {
+      bool tie_aborted = false;
+      if (unordered) SBX_TRY(ubfs_pick_root(h, c, r, &tie_aborted, true));
+      if (unordered && tie_aborted) {
+        deep = true;
+        unordered = false;
+        SBX_TRY(redo_sweep_ordered(h, c, root, &r));
+      } else if (!unordered) {
+        SBX_TRY(pick_root_ordered(h, c, r));
+      }
+    }
+    if (!unordered) SBX_TRY(reset_ppos(h, (const I *)c.q, r.count, c.ppos, c.n));
+    if (path) break;
+  }
+  // Cuthill-McKee BFS from the pseudo-peripheral vertex (:118-144)
+  if (!out.cm_done) {
+    SBX_TRY(c.join_ranks());
+    SBX_TRY(run_bfs<true>(h, c, -1, root, &r));
+    out.sweeps++;
+    out.levels += r.levels;
+  }
+  if ((int64_t)r.count != (int64_t)size)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbx_rcm_reorder: BFS reached %u of %d vertices of a component (pattern not symmetric?)",
+             r.count, size);
+  return SBX_OK;
+}
+
+// ---- the steps of a call, in the order sbx_rcm_reorder takes them -----------------------------------------------------
+static int alloc_buffers(sbx_handle_t h, RcmCall &c) {
+  const int64_t n = c.n;
+  SBX_TRY(sbx_salloc(h, 1, &c.dv));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.did_a));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.drank));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.label_buf));
+  SBX_TRY(sbx_salloc(h, (size_t)n + 1, &c.csize));
+  SBX_TRY(sbx_salloc(h, (size_t)n + 1, &c.cbase));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.small_list));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.large_list));
+  SBX_TRY(sbx_salloc(h, (size_t)n / (RCM_SMALL + 1) + 1, &c.mid_list));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.big_list));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.q));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.nf_list));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.dist));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.ppos));
+  // the three bitmaps share one allocation (64-bit aligned pieces): vbits and fbits are cleared together
+  const size_t bm_words = (((size_t)(n + 31) / 32 + 1) + 1) & ~(size_t)1;
+  SBX_TRY(sbx_salloc(h, 3 * bm_words, &c.vbits));
+  c.fbits = c.vbits + bm_words, c.cbits = c.fbits + bm_words;
+  SBX_TRY(sbx_salloc(h, bm_words, &c.ebits));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.q_small));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.lpos));
+  c.heavy_cap = (uint64_t)(size_t)(c.nnz / RCM_LIGHT + c.nnz / RCM_CHUNK + 1024);
+  SBX_TRY(sbx_salloc(h, (size_t)c.heavy_cap, &c.heavy));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.ka));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &c.kb));
+  // (dv is cleared by k_deg_reduce; csize, dist and ppos get their initial values from k_deg_count)
+  c.gn = sbx_grid_for(n, 256, 8192);
+  c.bm_bytes = (size_t)((n + 31) / 32) * sizeof(unsigned);
+  SBX_TRY(sbx_salloc(h, (size_t)DEG_UNITS * 4, &c.ucnt));
+  SBX_TRY(sbx_salloc(h, (size_t)std::max<int64_t>((int64_t)h->num_cus * 8, RCM_DIR_MAX), &c.hub_dir));
+  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 + 1, &c.fresh64));
+  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 + 1, &c.wcnt));
+  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 / RCM_FW_WORDS + 2, &c.woff));
+  SBX_TRY(sbx_salloc(h, sbx_cs::scratch_words(std::min<int64_t>(n, RCM_COUNT_SORT_MAX)), &c.cs_scratch));
+  SBX_TRY(sbx_salloc(h, (size_t)n + 64, &c.claim8));
+  SBX_TRY(sbx_salloc(h, (size_t)(c.bm_bytes / sizeof(unsigned)) + 2, &c.nbits));
+  SBX_TRY(sbx_salloc(h, (size_t)(c.bm_bytes / sizeof(unsigned)) + 2, &c.cone));
+  return SBX_OK;
+}
+
+// (1) global (degree,id) rank used by the Cuthill-McKee keys; first non-isolated vertex
+static int degree_counts(sbx_handle_t h, RcmCall &c) {
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_count, dim3(DEG_UNITS / 4), dim3(256), c.rp, c.n, c.ucnt, c.csize, c.dist, c.ppos,
+              (unsigned long long *)c.ebits);
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_reduce, dim3(1), dim3(1024), (const unsigned *)c.ucnt, c.dv);
+  SBX_LAUNCH_CHECK(h);
+  // after a grid barrier gave up (a GPU shared with another process, see gb_wait) the next few calls on this handle do
+  // not try the persistent kernels again
+  c.unordered_ok = sbx_sw().rcm_unordered && h->rcm_gb_backoff == 0;
+  if (h->rcm_gb_backoff > 0) h->rcm_gb_backoff--;
+  // The degree counts (non-empty rows, largest degree, first non-empty vertex) are read back with the first sweep's first
+  // round trip when that sweep is an unordered one: it starts from dv->root, which k_deg_reduce set, and needs nothing
+  // else the host does not know yet.  (~17 us per call: a read-back kernel and a launch gap.)
+  // (only with the side stream: without one the degree ranks are enqueued before the first sweep and need the counts)
+  c.lazy_counts = c.unordered_ok && !h->prof_on && sbx_sw().rcm_overlap;
+  if (!c.lazy_counts) {
+    RcmDev d;
+    SBX_TRY(sbx_readback(h, &d, c.dv, sizeof(RcmDev)));
+    c.take_counts(d);
+  }
+  c.main_stream = h->stream;
+  c.side = !h->prof_on && sbx_sw().rcm_overlap;
+  if (c.side) {  // (recorded here: the side stream waits for the counts above, not for the sweep enqueued before its work)
+    SBX_TRY(sbx_aux_streams(h));
+    SBX_HIP(h, hipEventRecord(h->aux_event[0], c.main_stream));
+  }
+  // with a side stream the first sweep's first kernel is enqueued first (the host's ~15 enqueues for the ranks then
+  // run while that kernel does); without one the ranks simply come first
+  if (!c.side) SBX_TRY(c.enqueue_ranks());
+  c.ranks_joined = !c.side;
+  // (every sweep of the call, on this stream or on one forked from it later, runs behind k_deg_count above — the lazy
+  // read-back of its counts changes what the HOST knows, not the stream order — so no level meets an unbuilt ebits)
+  return SBX_OK;
+}
+
+// (2) The smallest non-isolated vertex v0 is the smallest id of its component, i.e. the
+// start of that component's pseudo-peripheral search.  Its first BFS sweep is needed
+// anyway and yields the component's membership for free, so the union-find below only
+// has to label what that sweep did not reach (for power-law inputs: a sliver).
+// Sweeps of the pseudo-peripheral search run unordered (level sets only, run_ubfs) unless the component turns out deep
+// and narrow.
+static int first_sweep(sbx_handle_t h, RcmCall &c) {
+  bool deep0 = true;
+  if (!c.counts_ready) {  // the first sweep, from the root on the device; the counts come back with its first read-back
+    SBX_TRY(run_ubfs(h, c, (I)-1, (I)-1, &c.r0, &deep0));
+    if (!c.counts_ready) SBX_FAIL(h, SBX_ERR_INTERNAL, "sbx_rcm_reorder: the first sweep returned without a read-back");
+  }
+  if (c.lazy_counts) c.head_chain = false;
+  c.v0 = c.counts.first_vertex == UNSEEN ? (I)-1 : (I)c.counts.first_vertex;
+  if (c.v0 < 0) {  // not one edge: the sweep above (if any) started from an empty row and means nothing
+    c.r0.count = 0;
+    SBX_HIP(h, hipMemsetAsync(c.cbits, 0, c.bm_bytes, h->stream));  // (else: a copy of the first sweep's visited bitmap)
+    return SBX_OK;
+  }
+  bool deep = deep0;
+  if (!c.lazy_counts && c.unordered_ok) SBX_TRY(run_ubfs(h, c, c.v0, (I)-1, &c.r0, &deep));
+  c.head_chain = false;
+  c.r0_unordered = !deep;
+  c.unordered_sweeps += c.r0_unordered;
+  if (deep) SBX_TRY(run_bfs<false>(h, c, c.v0, (I)-1, &c.r0));
+  const int64_t bm_words = (int64_t)(c.bm_bytes / sizeof(unsigned));
+  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_copy_words, dim3(sbx_grid_for(bm_words, 256, 1024)), dim3(256), c.cbits,
+              (const unsigned *)c.vbits, bm_words);
+  SBX_LAUNCH_CHECK(h);
+  return SBX_OK;
+}
+
+// (3) connected components of the rest, in line or beside the first component's search; leaves the labelling's
+// counters in c.hd and what they mean for the rest of the call (n_host, mid_batched, first_is_large)
+static int label_rest(sbx_handle_t h, RcmCall &c) {
+  const I v0 = c.v0;
+  // When the first sweep reached every non-empty row there is no rest: one kernel places the empty rows and the stage
+  // ends (a power-law input: ~0.2 ms of union-find, size scan, classification and two round trips saved)
+  c.single_component = v0 >= 0 && (int64_t)c.r0.count == c.n_ranked && c.r0.count > (unsigned)RCM_MID;
+  if (c.single_component) {
+    SBX_KLAUNCH(h, SBX_K_CC, k_iso_positions, dim3(DEG_UNITS / 4), dim3(256), c.rp, c.n, (const unsigned *)c.ucnt, v0,
+                (I)c.r0.count, c.inv);
+    SBX_LAUNCH_CHECK(h);
+    c.hd.n_large = 1;
+    c.hd.n_components = (unsigned)(c.n - c.n_ranked) + 1u;
+    c.hd.n_empty_rows = (unsigned)(c.n - c.n_ranked);
+    c.n_host = 1;
+    c.first_is_large = true;
+    return SBX_OK;
+  }
+  // The first sweep's component, when it is one the host orders anyway (more than RCM_MID vertices), does not wait for
+  // the labelling of the rest: union-find, size scan and classification — streaming passes over all n vertices, 0.13 ms
+  // on the bench matrix — run on a side stream while the caller's stream goes on with that component's search and
+  // Cuthill-McKee sweep, which are bound by launches and latency, not by bandwidth.  The search needs no labels (a sweep
+  // cannot leave its component; unlabelled, the bottom-up levels merely look at the other components' vertices too).
+  c.cc_forked = c.side && v0 >= 0 && c.r0.count > (unsigned)RCM_MID && c.r0_unordered && sbx_sw().rcm_cc_overlap;
+  bool counters_read = false;
+  if (c.cc_forked) {
+    // The side stream's ten launches are enqueued behind the search's first kernels (the hook every sweep and tie-break
+    // calls before its first read-back, RcmCall::after_first_launch): the host needs ~50 us for them, which the caller's
+    // stream would spend idle.
+    SBX_HIP(h, hipEventRecord(h->aux_event[2], c.main_stream));
+    h->aux_dirty = true;
+    SBX_TRY(search_component(h, c, v0, (I)c.r0.count, true, c.sd0));
+    SBX_TRY(c.enqueue_cc());  // (a search that never waited for anything)
+    SBX_TRY(c.enqueue_cc());
+    c.comp0_searched = true;
+    if (!c.cc_joined) SBX_HIP(h, hipStreamWaitEvent(c.main_stream, h->aux_event[3], 0));
+    c.cc_forked = false;
+    if (c.ranks_joined || !c.ranks_enqueued) h->aux_dirty = false;
+    c.small_on_side = true;
+    // (the search's last sweep joined the side stream at its start and read *dv behind that: the labelling's counters
+    // are in that read-back already)
+    if (c.cc_joined && c.last_read_joined) c.hd = c.last_read, counters_read = true;
+  } else {
+    SBX_TRY(c.enqueue_cc_kernels(2));
+  }
+  if (!counters_read) SBX_TRY(sbx_readback(h, &c.hd, c.dv, sizeof(RcmDev)));
+  if (c.comp0_searched) {
+    // the component's order is complete in q: written now, its place read from the size scan on the device — BEHIND the
+    // read-back of the labelling's counters: when this component is the only one the host orders that read-back was the
+    // call's last and the kernel finishes in stream order after the call has returned (outputs are complete in stream
+    // order, as for every entry point that does not end in a read-back)
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_write_component, dim3(sbx_grid_for(c.sd0.r.count, 256, 4096)), dim3(256),
+                (const I *)c.q, c.sd0.r.count, (I)0, c.inv, (const I *)(c.cbase + v0));
+    SBX_LAUNCH_CHECK(h);
+  }
+  if (c.hd.unsym)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG,
+             "sbx_rcm_reorder: the pattern is not structurally symmetric (a vertex hangs under the first component "
+             "without being reachable from it); RCM is defined on symmetric patterns");
+  c.label = c.label_buf;
+  // Components of RCM_SMALL + 1 .. RCM_MID vertices: a few of them are ordered like the large ones (level-synchronous
+  // sweeps driven from the host: ~60 us per level, fine for a handful); from RCM_MID_BATCH on they join the batched
+  // kernel, one lane each — a collection of 10^5 meshes of a few hundred vertices is then one launch instead of
+  // 10^5 host-driven searches.
+  c.mid_batched = c.hd.n_mid >= (unsigned)RCM_MID_BATCH;
+  c.n_host = c.hd.n_large + (c.mid_batched ? 0u : c.hd.n_mid);
+  c.first_is_large = c.r0.count > (unsigned)RCM_SMALL && !(c.mid_batched && c.r0.count <= (unsigned)RCM_MID);
+  return SBX_OK;
+}
+
+// (3) small (and, batched, mid-size) components: one lane each
+static int order_small_components(sbx_handle_t h, RcmCall &c) {
+  if (c.single_component) return SBX_OK;
+  // the pre-swept component is handled by the batched kernel: drop the sweep's marks
+  if (c.v0 >= 0 && !c.first_is_large && !c.r0_unordered) SBX_TRY(reset_ppos(h, (const I *)c.q, c.r0.count, c.ppos, c.n));
+  if (c.hd.n_small && !c.small_on_side) {
+    SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3((c.hd.n_small + 63) / 64), dim3(64), c.rp, c.col,
+                (const I *)c.small_list, c.hd.n_small, (const I *)c.csize, (const I *)c.cbase, c.dist, c.q_small, c.inv,
+                c.dv, (const unsigned *)nullptr);
+    SBX_LAUNCH_CHECK(h);
+  }
+  if (c.mid_batched) {
+    SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3((c.hd.n_mid + 63) / 64), dim3(64), c.rp, c.col,
+                (const I *)c.mid_list, c.hd.n_mid, (const I *)c.csize, (const I *)c.cbase, c.dist, c.q_small, c.inv, c.dv,
+                (const unsigned *)nullptr);
+    SBX_LAUNCH_CHECK(h);
+  }
+  return SBX_OK;
+}
+
+// (4) large components: host-driven level-synchronous BFS
+static int order_host_components(sbx_handle_t h, RcmCall &c) {
+  const unsigned n_host = c.n_host;
+  const RcmDev &hd = c.hd;
+  const I v0 = c.v0;
+  if (!n_host) return SBX_OK;
+  std::vector<I> roots(n_host), sizes(n_host), bases(n_host);
+  I *info = nullptr;  // roots | sizes | bases, gathered on the device: three copies whatever the component count
+  SBX_TRY(sbx_salloc(h, (size_t)3 * n_host, &info));
+  if (c.single_component) {  // root v0; every vertex in front of it has an empty row, i.e. is a component of its own
+    roots[0] = v0, sizes[0] = (I)c.r0.count, bases[0] = v0;
+  } else if (c.comp0_searched && n_host == 1) {  // (already written, its place taken from the device)
+    roots[0] = v0, sizes[0] = (I)c.r0.count, bases[0] = 0;
+  } else {
+    if (hd.n_large)
+      SBX_HIP(h, hipMemcpyAsync(info, c.large_list, hd.n_large * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
+    if (!c.mid_batched && hd.n_mid)
+      SBX_HIP(h, hipMemcpyAsync(info + hd.n_large, c.mid_list, hd.n_mid * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
+    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_comp_info, dim3((n_host + 255) / 256), dim3(256), (const I *)info, n_host,
+                (const I *)c.csize, (const I *)c.cbase, info + n_host, info + 2 * (size_t)n_host);
+    SBX_LAUNCH_CHECK(h);
+    if (n_host <= 64) {  // the usual case, a few components: one polled read-back instead of three copies and a sync
+      I tmp[3 * 64];
+      SBX_TRY(sbx_readback(h, tmp, info, (size_t)3 * n_host * sizeof(I)));
+      for (unsigned k = 0; k < n_host; k++) roots[k] = tmp[k], sizes[k] = tmp[n_host + k], bases[k] = tmp[2 * n_host + k];
+    } else {
+      SBX_HIP(h, hipMemcpyAsync(roots.data(), info, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
+      SBX_HIP(h, hipMemcpyAsync(sizes.data(), info + n_host, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
+      SBX_HIP(h, hipMemcpyAsync(bases.data(), info + 2 * (size_t)n_host, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
+      SBX_HIP(h, hipStreamSynchronize(h->stream));
+    }
+  }
+  // the pre-swept component goes first: its sweep state (q, ppos) is still live
+  for (unsigned k = 1; k < n_host; k++)
+    if (c.first_is_large && roots[k] == v0) {
+      std::swap(roots[k], roots[0]);
+      std::swap(sizes[k], sizes[0]);
+      std::swap(bases[k], bases[0]);
+    }
+  for (unsigned k = 0; k < n_host; k++) {
+    const bool searched_before = k == 0 && c.comp0_searched;  // (beside its labelling: label_rest, written there too)
+    Searched sd;
+    if (searched_before) sd = c.sd0;
+    else SBX_TRY(search_component(h, c, roots[k], sizes[k], c.first_is_large && roots[k] == v0, sd));
+    const BfsResult &r = sd.r;
+    if (!searched_before) {
+      SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_write_component, dim3(sbx_grid_for(r.count, 256, 4096)), dim3(256),
+                  (const I *)c.q, r.count, bases[k], c.inv, (const I *)nullptr);
+      SBX_LAUNCH_CHECK(h);
+    }
+    // invariant of the sweeps (k_visited_from_ppos relies on it): ppos is UNSEEN outside the running sweep
+    if (k + 1 < n_host) SBX_TRY(reset_ppos(h, (const I *)c.q, r.count, c.ppos, c.n));
+    if (sizes[k] > c.largest) {
+      c.largest = sizes[k];
+      c.sweeps_max = sd.sweeps;
+      c.levels_max = sd.levels;
+      // what the reference's serial algorithm runs on this component: its pseudo-peripheral sweeps (a speculative
+      // Cuthill-McKee sweep that ended the search stood in for the last of them) + the Cuthill-McKee sweep
+      c.ref_sweeps_max = sd.candidate + (sd.cm_done ? 1 : 0) + 1;
+    }
+  }
+  return SBX_OK;
+}
+
+// the call's last read-back (also its synchronisation point) and the statistics
+static int finish(sbx_handle_t h, RcmCall &c, sbx_rcm_stats *stats_host) {
+  const RcmDev &hd = c.hd;
+  SBX_TRY(c.join_ranks());  // inputs without a large component never ran a Cuthill-McKee sweep
+  RcmDev fin;
+  if (c.comp0_searched && c.n_host == 1 && !c.mid_batched) fin = hd;  // nothing was launched behind that read-back
+  else SBX_TRY(sbx_readback(h, &fin, c.dv, sizeof(RcmDev)));
+  if (fin.unsym)
+    SBX_FAIL(h, SBX_ERR_BAD_ARG,
+             "sbx_rcm_reorder: the pattern is not structurally symmetric (a BFS cannot reach its whole component); "
+             "RCM is defined on symmetric patterns");
+  if (stats_host) {
+    stats_host->small_components = hd.n_small + (c.mid_batched ? hd.n_mid : 0u);
+    stats_host->large_components = c.n_host;
+    stats_host->bfs_sweeps = c.sweeps_max;
+    stats_host->bfs_levels = c.levels_max;
+    stats_host->edges_scanned = (int64_t)(fin.edges + fin.edges_bu);  // (a bottom-up kernel counts in edges_bu alone)
+    stats_host->edges_scanned_bottom_up = (int64_t)fin.edges_bu;
+    stats_host->largest_component = c.largest;
+    stats_host->components = (int64_t)hd.n_components;
+    stats_host->isolated = (int64_t)hd.n_empty_rows;
+    stats_host->reference_sweeps = c.ref_sweeps_max;
+    stats_host->unordered_sweeps = c.unordered_sweeps;
   }
   return SBX_OK;
 }
@@ -4315,532 +4832,15 @@ int SBX_RCM_ENTRY(sbx_handle_t h, int64_t n, int64_t nnz, const void *row_ptr, c
   SBX_TRY(sbx_arena_begin(h));
   sbx_aux_scope aux_scope(h);  // (degree ranks, component labelling, split expansion: no way out leaves a fork open)
   if (n == 0) return SBX_OK;
-  const X *rp = (const X *)row_ptr, *col = (const X *)col_v;
-  X *inv = (X *)inv_perm_out;
-
-  RcmDev *dv;
-  uint32_t *did_a, *drank;
-  I *label, *csize, *cbase, *small_list, *mid_list, *large_list, *big_list, *q, *nf_list;
-  unsigned *dist, *ppos, *vbits, *fbits, *cbits, *lpos;
-  I *q_small;
-  uint64_t *ka, *kb, *heavy;
-  SBX_TRY(sbx_salloc(h, 1, &dv));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &did_a));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &drank));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &label));
-  SBX_TRY(sbx_salloc(h, (size_t)n + 1, &csize));
-  SBX_TRY(sbx_salloc(h, (size_t)n + 1, &cbase));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &small_list));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &large_list));
-  SBX_TRY(sbx_salloc(h, (size_t)n / (RCM_SMALL + 1) + 1, &mid_list));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &big_list));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &q));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &nf_list));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &dist));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ppos));
-  // the three bitmaps share one allocation (64-bit aligned pieces): vbits and fbits are cleared together
-  const size_t bm_words = (((size_t)(n + 31) / 32 + 1) + 1) & ~(size_t)1;
-  SBX_TRY(sbx_salloc(h, 3 * bm_words, &vbits));
-  fbits = vbits + bm_words;
-  cbits = fbits + bm_words;
-  unsigned *ebits;  // the empty rows (k_deg_count below): with vbits, the candidates of every bottom-up level
-  SBX_TRY(sbx_salloc(h, bm_words, &ebits));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &q_small));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &lpos));
-  const size_t heavy_cap = (size_t)(nnz / RCM_LIGHT + nnz / RCM_CHUNK + 1024);
-  SBX_TRY(sbx_salloc(h, heavy_cap, &heavy));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ka));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &kb));
-  // (dv is cleared by k_deg_reduce; csize, dist and ppos get their initial values from k_deg_count)
-
-  const unsigned gn = sbx_grid_for(n, 256, 8192);
-  const size_t bm_bytes = (size_t)((n + 31) / 32) * sizeof(unsigned);
-  // (1) global (degree,id) rank used by the Cuthill-McKee keys; first non-isolated vertex
-  unsigned *ucnt = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)DEG_UNITS * 4, &ucnt));  // per unit: non-empty rows, largest degree, first non-empty vertex, rows of 255+ entries
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_count, dim3(DEG_UNITS / 4), dim3(256), rp, n, ucnt, csize, dist, ppos,
-              (unsigned long long *)ebits);
-  SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_deg_reduce, dim3(1), dim3(1024), (const unsigned *)ucnt, dv);
-  SBX_LAUNCH_CHECK(h);
-  // after a grid barrier gave up (a GPU shared with another process, see gb_wait) the next few calls on this handle do
-  // not try the persistent kernels again
-  const bool unordered_ok = sbx_sw().rcm_unordered && h->rcm_gb_backoff == 0;
-  if (h->rcm_gb_backoff > 0) h->rcm_gb_backoff--;
-  // The degree counts (non-empty rows, largest degree, first non-empty vertex) are read back with the first sweep's first
-  // round trip when that sweep is an unordered one: it starts from dv->root, which k_deg_reduce set, and needs nothing
-  // else the host does not know yet.  (~17 us per call: a read-back kernel and a launch gap.)
-  // (only with the side stream: without one the degree ranks are enqueued before the first sweep and need the counts)
-  const bool lazy_counts = unordered_ok && !h->prof_on && sbx_sw().rcm_overlap;
-  RcmDev hd0;
-  bool hd0_ready = false;
-  if (!lazy_counts) {
-    SBX_TRY(sbx_readback(h, &hd0, dv, sizeof(RcmDev)));
-    hd0_ready = true;
-  }
-  int64_t n_ranked = hd0_ready ? (int64_t)hd0.n_nonempty : 0;  // vertices that get a degree rank
-  // Only the Cuthill-McKee sweep reads the degree ranks: they are built on a side stream while the plain sweeps —
-  // launch- and latency-bound — run on the caller's stream, and joined before the first Cuthill-McKee sweep.
-  const uint32_t *dorder = nullptr;
-  hipStream_t main_stream = h->stream;
-  const bool side = !h->prof_on && sbx_sw().rcm_overlap;
-  BfsBuffers b;
-  if (side) {  // (recorded here: the side stream waits for the counts above, not for the sweep enqueued before its work)
-    SBX_TRY(sbx_aux_streams(h));
-    SBX_HIP(h, hipEventRecord(h->aux_event[0], main_stream));
-  }
-  bool ranks_enqueued = false;
-  bool cc_forked = false;  // the labelling of the other components is running on a side stream of its own (below)
-  std::function<int()> enqueue_ranks = [&]() -> int {
-    if (ranks_enqueued) return SBX_OK;
-    ranks_enqueued = true;
-    if (side) {
-      void *slot = nullptr;
-      SBX_TRY(sbx_arena_alloc(h, SBX_RS_SLOT_BYTES, &slot));
-      SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[0], h->aux_event[0], 0));
-      h->aux_dirty = true;
-      h->stream = h->aux_stream[0];
-      if (hipMemsetAsync(slot, 0, SBX_RS_SLOT_BYTES, h->stream) != hipSuccess) {
-        h->stream = main_stream;
-        SBX_FAIL(h, SBX_ERR_HIP, "sbx_rcm_reorder: hipMemsetAsync failed");
-      }
-      h->rs_override = slot;
-    }
-    int rc = SBX_OK;
-    // one stable counting pass on min(degree, 255) over the rows in id order + the last bucket by its full degree
-    // (sbx_degree.hip): 0.09 ms where a generic sort of (degree, id) pairs took 0.31
-    // (hd0 — not the locals derived from it: this hook may run inside the first sweep, right behind the read-back that
-    // delivered the counts)
-    rc = sbx_degree_ranks(h, SBX_RCM_IT, rp, n, (int64_t)hd0.n_nonempty, (int64_t)hd0.n_top, hd0.max_deg, drank, did_a);
-    dorder = did_a;
-    b.dorder = dorder;
-    if (side && rc == SBX_OK && hipEventRecord(h->aux_event[1], h->stream) != hipSuccess) rc = SBX_ERR_HIP;
-    h->stream = main_stream;
-    h->rs_override = nullptr;
-    return rc;
-  };
-  // with a side stream the first sweep's first kernel is enqueued first (the host's ~15 enqueues for the ranks then
-  // run while that kernel does); without one the ranks simply come first
-  if (!side) SBX_TRY(enqueue_ranks());
-  bool ranks_joined = !side;
-  auto join_ranks = [&]() -> int {
-    if (!ranks_enqueued) SBX_TRY(enqueue_ranks());
-    if (!ranks_joined) {
-      SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[1], 0));
-      ranks_joined = true;
-      if (!cc_forked) h->aux_dirty = false;
-    }
-    return SBX_OK;
-  };
-  bool claim_clean = false;
-  b.claim_clean = &claim_clean;
-  b.after_first_launch = &enqueue_ranks;
-  b.hook_wants_long_cover = true;  // (~15 launches)
-  b.head_chain = true;  // (until the first sweep has run)
-  bool tie_unverified = false;
-  b.tie_unverified = &tie_unverified;
-  b.side_stage = nullptr, b.side_event = nullptr, b.side_joined = nullptr, b.last_read = nullptr, b.last_read_joined = nullptr;
-  b.rp = rp; b.col = col; b.vbits = vbits; b.fbits = fbits; b.lpos = lpos; b.ppos = ppos; b.label = nullptr;
-  // (every sweep of the call, on this stream or on one forked from it later, runs behind k_deg_count above — the lazy
-  // read-back of its counts changes what the HOST knows, not the stream order — so no level meets an unbuilt bitmap)
-  b.ebits = ebits;
-  b.nnz = nnz; b.q = q; b.nf_list = nf_list; b.heavy = heavy; b.heavy_cap = heavy_cap;
-  SBX_TRY(sbx_salloc(h, (size_t)std::max<int64_t>((int64_t)h->num_cus * 8, RCM_DIR_MAX), &b.hub_dir));
-  b.ka = ka; b.kb = kb; b.drank = drank; b.dorder = dorder; b.n_ranked = n_ranked; b.dv = dv; b.n = n;
-  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 + 1, &b.fresh64));
-  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 + 1, &b.wcnt));
-  SBX_TRY(sbx_salloc(h, (size_t)(n + 63) / 64 / RCM_FW_WORDS + 2, &b.woff));
-  SBX_TRY(sbx_salloc(h, sbx_cs::scratch_words(std::min<int64_t>(n, RCM_COUNT_SORT_MAX)), &b.cs_scratch));
-  b.max_deg = hd0_ready ? hd0.max_deg : 0u;
-  b.late_counts = hd0_ready ? nullptr : &hd0;
-  b.late_counts_ready = &hd0_ready;
-  // (2) The smallest non-isolated vertex v0 is the smallest id of its component, i.e. the
-  // start of that component's pseudo-peripheral search.  Its first BFS sweep is needed
-  // anyway and yields the component's membership for free, so the union-find below only
-  // has to label what that sweep did not reach (for power-law inputs: a sliver).
-  BfsResult r0;
-  r0.count = 0;
-  // sweeps of the pseudo-peripheral search run unordered (level sets only, run_ubfs) unless the component turns out
-  // deep and narrow
-  unsigned char *claim8 = nullptr;
-  unsigned *cone = nullptr, *nbits = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)n + 64, &claim8));
-  SBX_TRY(sbx_salloc(h, (size_t)(bm_bytes / sizeof(unsigned)) + 2, &nbits));
-  SBX_TRY(sbx_salloc(h, (size_t)(bm_bytes / sizeof(unsigned)) + 2, &cone));
-  bool r0_unordered = false;
-  bool deep0 = true;
-  int64_t unordered_sweeps = 0;  // sweeps that kept the level sets only (statistics; the tests check the path was taken)
-  if (!hd0_ready) {  // the first sweep, from the root on the device; the counts come back with its first read-back
-    SBX_TRY(run_ubfs(h, b, claim8, nbits, cone, (I)-1, (I)-1, &r0, &deep0));
-    if (!hd0_ready) SBX_FAIL(h, SBX_ERR_INTERNAL, "sbx_rcm_reorder: the first sweep returned without a read-back");
-    n_ranked = (int64_t)hd0.n_nonempty;
-    b.n_ranked = n_ranked;
-    b.max_deg = hd0.max_deg;
-    b.late_counts = nullptr;
-  }
-  if (hd0_ready && lazy_counts) b.head_chain = false;
-  const I v0 = hd0.first_vertex == UNSEEN ? (I)-1 : (I)hd0.first_vertex;
-  if (v0 < 0) {  // not one edge: the sweep above (if any) started from an empty row and means nothing
-    r0.count = 0;
-    deep0 = true;
-    SBX_HIP(h, hipMemsetAsync(cbits, 0, bm_bytes, h->stream));  // (else: a copy of the first sweep's visited bitmap)
-  }
-  if (v0 >= 0) {
-    bool deep = deep0;
-    if (!lazy_counts && unordered_ok) SBX_TRY(run_ubfs(h, b, claim8, nbits, cone, v0, (I)-1, &r0, &deep));
-    b.head_chain = false;
-    r0_unordered = !deep;
-    unordered_sweeps += r0_unordered;
-    if (deep) SBX_TRY(run_bfs<false>(h, b, v0, (I)-1, &r0));
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_copy_words, dim3(sbx_grid_for((int64_t)(bm_bytes / sizeof(unsigned)), 256, 1024)),
-                dim3(256), cbits, (const unsigned *)vbits, (int64_t)(bm_bytes / sizeof(unsigned)));
-    SBX_LAUNCH_CHECK(h);
-  }
-  // Pseudo-peripheral search and Cuthill-McKee sweep of one host-ordered component (root = its smallest vertex): leaves
-  // the component's order in q.
-  struct Searched {
-    BfsResult r;
-    int64_t sweeps, levels, candidate;
-    bool cm_done;
-  };
-  Searched sd0;
-  bool comp0_searched = false, small_on_side = false;
-  auto search_component = [&](I root, I size, bool have_first_sweep, Searched &out) -> int {
-    BfsResult &r = out.r;
-    int64_t prev_ecc = -1, ecc = 0;
-    int64_t &sweeps = out.sweeps, &levels = out.levels, &candidate = out.candidate;
-    sweeps = levels = candidate = 0;
-    I fixed = root;
-    bool &cm_done = out.cm_done;
-    cm_done = false;
-    bool deep = !unordered_ok;  // a sweep of more than UB_MAX_LEVELS levels: this component keeps ordered sweeps
-    while (prev_ecc != ecc) {
-      prev_ecc = ecc;
-      bool unordered = false;  // the sweep just run kept no order inside its levels
-      if (have_first_sweep) {
-        r = r0;  // sweep (2) above was exactly this component's first sweep
-        have_first_sweep = false;
-        unordered = r0_unordered;
-        if (!unordered) deep = true;
-      } else {
-        // (a sweep behind an unverified tie walk comes back at once when the walk had left: the persistent kernels then
-        // finish the tie-break on the sweep r still describes — exactly what followed the tie-break before — and the
-        // sweep is enqueued again)
-        auto settle_tie = [&]() -> int {
-          bool ab = false;
-          SBX_TRY(ubfs_pick_root_slow(h, b, cone, r, &ab, true));
-          if (ab) {  // a grid barrier of the tie-break gave up: the same sweep again, ordered (dv->root still is its root)
-            deep = true;
-            SBX_TRY(run_bfs<false>(h, b, -1, root, &r));
-            SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_pick_root, dim3(sbx_grid_for(r.last_size, 256, 1024)), dim3(256), rp,
-                        (const I *)(q + r.last_offset), r.last_size, dv);
-            SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_set_root_from_best, dim3(1), dim3(1), (const I *)(q + r.last_offset), dv);
-            SBX_TRY(reset_ppos(h, (const I *)q, r.count, ppos, n));
-          }
-          return SBX_OK;
-        };
-        if (candidate >= RCM_SPECULATE_FROM) {
-          SBX_TRY(join_ranks());
-          bool sf = false;
-          SBX_TRY(run_bfs<true>(h, b, fixed, root, &r, &sf));
-          if (sf) {
-            SBX_TRY(settle_tie());
-            SBX_TRY(run_bfs<true>(h, b, (I)-1, root, &r));
-          }
-          sweeps++;
-          levels += r.levels;
-          const int64_t e = (int64_t)r.levels - 1;
-          const int64_t deepest = e > ecc ? e : ecc;
-          if (deepest == ecc || (int64_t)r.count == deepest + 1) {
-            cm_done = true;  // this candidate is the root and q already holds its Cuthill-McKee order
-            break;
-          }
-          SBX_TRY(reset_ppos(h, (const I *)q, r.count, ppos, n));
-          fixed = -1;  // k_bfs_start left the root on the device
-        }
-        if (!deep) {
-          bool sf = false;
-          SBX_TRY(run_ubfs(h, b, claim8, nbits, cone, fixed, root, &r, &deep, &sf));
-          if (sf) {
-            SBX_TRY(settle_tie());
-            if (!deep) SBX_TRY(run_ubfs(h, b, claim8, nbits, cone, (I)-1, root, &r, &deep));
-          }
-          unordered = !deep;
-          unordered_sweeps += unordered;
-        }
-        if (deep) SBX_TRY(run_bfs<false>(h, b, fixed, root, &r));
-      }
-      fixed = -1;  // later sweeps start from the device-resident root
-      candidate++;
-      sweeps++;
-      levels += r.levels;
-      const int64_t e = (int64_t)r.levels - 1;
-      if (e > ecc) ecc = e;
-      const bool path = (int64_t)r.count == ecc + 1;
-      if (!path && prev_ecc != ecc) {
-        bool tie_aborted = false;
-        if (unordered) SBX_TRY(ubfs_pick_root(h, b, cone, r, &tie_aborted, true));
-        if (unordered && tie_aborted) {
-          // a grid barrier of the tie-break gave up: the same sweep again, ordered (dv->root still is its root)
-          deep = true;
-          unordered = false;
-          SBX_TRY(run_bfs<false>(h, b, -1, root, &r));
-        }
-        if (!unordered) {
-          SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_pick_root, dim3(sbx_grid_for(r.last_size, 256, 1024)), dim3(256), rp,
-                             (const I *)(q + r.last_offset), r.last_size, dv);
-          SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_set_root_from_best, dim3(1), dim3(1), (const I *)(q + r.last_offset), dv);
-        }
-      }
-      if (!unordered) SBX_TRY(reset_ppos(h, (const I *)q, r.count, ppos, n));
-      if (path) break;
-    }
-    // Cuthill-McKee BFS from the pseudo-peripheral vertex (:118-144)
-    if (!cm_done) {
-      SBX_TRY(join_ranks());
-      SBX_TRY(run_bfs<true>(h, b, -1, root, &r));
-      sweeps++;
-      levels += r.levels;
-    }
-    if ((int64_t)r.count != (int64_t)size)
-      SBX_FAIL(h, SBX_ERR_BAD_ARG,
-               "sbx_rcm_reorder: BFS reached %u of %d vertices of a component (pattern not symmetric?)", r.count,
-               size);
-    return SBX_OK;
-  };
-  // (3) connected components of the rest; the root of each tree is the component's smallest id.  When the first sweep
-  // reached every non-empty row there is no rest: one kernel places the empty rows and the stage ends (a power-law
-  // input: ~0.2 ms of union-find, size scan, classification and two round trips saved)
-  const bool single_component = v0 >= 0 && (int64_t)r0.count == n_ranked && r0.count > (unsigned)RCM_MID;
-  RcmDev hd;
-  memset(&hd, 0, sizeof(hd));
-  bool mid_batched = false;
-  unsigned n_host = 0;
-  bool first_is_large = false;
-  if (single_component) {
-    SBX_KLAUNCH(h, SBX_K_CC, k_iso_positions, dim3(DEG_UNITS / 4), dim3(256), rp, n, (const unsigned *)ucnt, v0, (I)r0.count,
-                inv);
-    SBX_LAUNCH_CHECK(h);
-    hd.n_large = 1;
-    hd.n_components = (unsigned)(n - n_ranked) + 1u;
-    hd.n_empty_rows = (unsigned)(n - n_ranked);
-    n_host = 1;
-    first_is_large = true;
-  } else {
-  // The first sweep's component, when it is one the host orders anyway (more than RCM_MID vertices), does not wait for
-  // the labelling of the rest: union-find, size scan and classification — streaming passes over all n vertices, 0.13 ms
-  // on the bench matrix — run on a side stream while the caller's stream goes on with that component's search and
-  // Cuthill-McKee sweep, which are bound by launches and latency, not by bandwidth.  The search needs no labels (a sweep
-  // cannot leave its component; unlabelled, the bottom-up levels merely look at the other components' vertices too).
-  cc_forked = side && v0 >= 0 && r0.count > (unsigned)RCM_MID && r0_unordered && sbx_sw().rcm_cc_overlap;
-  bool counters_read = false;
-  // (in two halves: on the side stream each half is enqueued behind one of the tie-break's ~45 us kernels)
-  auto enqueue_cc_kernels = [&](int half) -> int {
-  const unsigned gcount = gn < 1024u ? gn : 1024u;
-  if (half != 1) {
-  SBX_KLAUNCH(h, SBX_K_CC, k_cc_init, dim3(gn), dim3(256), rp, col, label, n, (const unsigned *)cbits);
-  SBX_KLAUNCH(h, SBX_K_CC, k_cc_hook_small, dim3(gn), dim3(256), rp, col, label, n, big_list,
-              (const unsigned *)cbits, dv);
-  SBX_KLAUNCH(h, SBX_K_CC, k_cc_hook_big, dim3((unsigned)h->num_cus * 8), dim3(256), rp, col, label,
-              (const I *)big_list, (const RcmDev *)dv);
-  // (phase 0 and the classification end in one counter add per workgroup: few workgroups, or the counter word is the
-  // bottleneck — 16 K adds on one word cost 0.19 ms)
-  for (int phase = 0; phase < 2; phase++)
-    SBX_KLAUNCH(h, SBX_K_CC, k_cc_finalize, dim3(phase == 0 ? gcount : gn), dim3(256), rp, label, csize, n,
-                (const unsigned *)cbits, v0 >= 0 ? v0 : (I)0, (I)r0.count, phase, dv);
-  SBX_LAUNCH_CHECK(h);
-  }
-  if (half != 0) {
-  SBX_TRY(sbx_exclusive_scan_i32(h, csize, cbase, n + 1, nullptr));
-  SBX_KLAUNCH(h, SBX_K_CC, k_classify, dim3(gcount), dim3(256), (const I *)label, (const I *)csize, (const I *)cbase, inv,
-              small_list, mid_list, large_list, n, dv);
-  SBX_LAUNCH_CHECK(h);
-  }
-  return SBX_OK;
-  };
-  if (cc_forked) {
-    // The side stream's ten launches are enqueued behind the search's first kernels (the hook every sweep and tie-break
-    // calls before its first read-back): the host needs ~50 us for them, which the caller's stream would spend idle.
-    SBX_HIP(h, hipEventRecord(h->aux_event[2], main_stream));
-    h->aux_dirty = true;
-    int cc_stage = 0;  // halves of the labelling enqueued so far
-    bool cc_joined = false, last_read_joined = false;
-    RcmDev last_read;
-    b.side_stage = &cc_stage, b.side_event = h->aux_event[3], b.side_joined = &cc_joined;
-    b.last_read = &last_read, b.last_read_joined = &last_read_joined;
-    // (a half per firing, behind any launch: both halves at one go behind a chain of big levels only — tried when the
-    // tie-breaks stopped being 80 us of persistent kernels to hide behind — looked better under the profiler, whose
-    // launches take 10 us of host time each, and cost 28 us on the wall clock: the side work simply started later)
-    std::function<int()> enqueue_cc = [&]() -> int {
-      SBX_TRY(enqueue_ranks());
-      if (cc_stage >= 2) return SBX_OK;
-      if (cc_stage == 0) SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[2], 0));
-      h->stream = h->aux_stream[1];
-      int rc = enqueue_cc_kernels(cc_stage);
-      if (rc == SBX_OK && cc_stage == 1) {  // the small components too: their number stays on the device, the launch covers any
-        const unsigned lanes = (unsigned)std::min<int64_t>((n / 2 + 63) / 64 * 64, (int64_t)h->num_cus * 32 * 64);
-        SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3(lanes / 64 > 0 ? lanes / 64 : 1), dim3(64), rp, col,
-                    (const I *)small_list, 0u, (const I *)csize, (const I *)cbase, dist, q_small, inv, dv,
-                    (const unsigned *)&dv->n_small);
-        if (hipGetLastError() != hipSuccess) rc = SBX_ERR_HIP;
-        if (rc == SBX_OK && hipEventRecord(h->aux_event[3], h->stream) != hipSuccess) rc = SBX_ERR_HIP;
-      }
-      cc_stage++;
-      h->stream = main_stream;
-      return rc;
-    };
-
-    b.after_first_launch = &enqueue_cc;
-    b.hook_wants_long_cover = false;  // (half a dozen launches per call)
-    const int src = search_component(v0, (I)r0.count, true, sd0);
-    b.after_first_launch = &enqueue_ranks;
-    b.hook_wants_long_cover = true;
-    b.side_stage = nullptr, b.side_joined = nullptr, b.last_read = nullptr, b.last_read_joined = nullptr;
-    if (src != SBX_OK) {  // (the side stream must not be left waiting for a half that never comes)
-      h->stream = main_stream;
-      return src;
-    }
-    SBX_TRY(enqueue_cc());  // (a search that never waited for anything)
-    SBX_TRY(enqueue_cc());
-    comp0_searched = true;
-    if (!cc_joined) SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[3], 0));
-    cc_forked = false;
-    if (ranks_joined || !ranks_enqueued) h->aux_dirty = false;
-    small_on_side = true;
-    // (the search's last sweep joined the side stream at its start and read *dv behind that: the labelling's counters
-    // are in that read-back already)
-    if (cc_joined && last_read_joined) hd = last_read, counters_read = true;
-  } else {
-    SBX_TRY(enqueue_cc_kernels(2));
-  }
-  if (!counters_read) SBX_TRY(sbx_readback(h, &hd, dv, sizeof(RcmDev)));
-  if (comp0_searched) {
-    // the component's order is complete in q: written now, its place read from the size scan on the device — BEHIND the
-    // read-back of the labelling's counters: when this component is the only one the host orders that read-back was the
-    // call's last and the kernel finishes in stream order after the call has returned (outputs are complete in stream
-    // order, as for every entry point that does not end in a read-back)
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_write_component, dim3(sbx_grid_for(sd0.r.count, 256, 4096)), dim3(256), (const I *)q,
-                sd0.r.count, (I)0, inv, (const I *)(cbase + v0));
-    SBX_LAUNCH_CHECK(h);
-  }
-  if (hd.unsym)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG,
-             "sbx_rcm_reorder: the pattern is not structurally symmetric (a vertex hangs under the first component "
-             "without being reachable from it); RCM is defined on symmetric patterns");
-  b.label = label;
-  // Components of RCM_SMALL + 1 .. RCM_MID vertices: a few of them are ordered like the large ones (level-synchronous
-  // sweeps driven from the host: ~60 us per level, fine for a handful); from RCM_MID_BATCH on they join the batched
-  // kernel, one lane each — a collection of 10^5 meshes of a few hundred vertices is then one launch instead of
-  // 10^5 host-driven searches.
-  mid_batched = hd.n_mid >= (unsigned)RCM_MID_BATCH;
-  n_host = hd.n_large + (mid_batched ? 0u : hd.n_mid);  // components ordered from the host
-  first_is_large = r0.count > (unsigned)RCM_SMALL && !(mid_batched && r0.count <= (unsigned)RCM_MID);
-  if (v0 >= 0 && !first_is_large && !r0_unordered) {
-    // the pre-swept component is handled by the batched kernel: drop the sweep's marks
-    SBX_TRY(reset_ppos(h, (const I *)q, r0.count, ppos, n));
-  }
-  // (3) small (and, batched, mid-size) components: one lane each
-  if (hd.n_small && !small_on_side) {
-    SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3((hd.n_small + 63) / 64), dim3(64), rp, col,
-                       (const I *)small_list, hd.n_small, (const I *)csize, (const I *)cbase, dist, q_small, inv, dv,
-                       (const unsigned *)nullptr);
-    SBX_LAUNCH_CHECK(h);
-  }
-  if (mid_batched) {
-    SBX_KLAUNCH(h, SBX_K_RCM_SMALL, k_rcm_small, dim3((hd.n_mid + 63) / 64), dim3(64), rp, col, (const I *)mid_list,
-                hd.n_mid, (const I *)csize, (const I *)cbase, dist, q_small, inv, dv, (const unsigned *)nullptr);
-    SBX_LAUNCH_CHECK(h);
-  }
-  }
-  // (4) large components: host-driven level-synchronous BFS
-  int64_t sweeps_max = 0, levels_max = 0, largest = 0, ref_sweeps_max = 0;
-  if (n_host) {
-    std::vector<I> roots(n_host), sizes(n_host), bases(n_host);
-    I *info = nullptr;  // roots | sizes | bases, gathered on the device: three copies whatever the component count
-    SBX_TRY(sbx_salloc(h, (size_t)3 * n_host, &info));
-    if (single_component) {  // root v0; every vertex in front of it has an empty row, i.e. is a component of its own
-      roots[0] = v0, sizes[0] = (I)r0.count, bases[0] = v0;
-    } else if (comp0_searched && n_host == 1) {  // (already written, its place taken from the device)
-      roots[0] = v0, sizes[0] = (I)r0.count, bases[0] = 0;
-    } else {
-    if (hd.n_large)
-      SBX_HIP(h, hipMemcpyAsync(info, large_list, hd.n_large * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
-    if (!mid_batched && hd.n_mid)
-      SBX_HIP(h, hipMemcpyAsync(info + hd.n_large, mid_list, hd.n_mid * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
-    SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_comp_info, dim3((n_host + 255) / 256), dim3(256), (const I *)info, n_host,
-                (const I *)csize, (const I *)cbase, info + n_host, info + 2 * (size_t)n_host);
-    SBX_LAUNCH_CHECK(h);
-    if (n_host <= 64) {  // the usual case, a few components: one polled read-back instead of three copies and a sync
-      I tmp[3 * 64];
-      SBX_TRY(sbx_readback(h, tmp, info, (size_t)3 * n_host * sizeof(I)));
-      for (unsigned c = 0; c < n_host; c++) roots[c] = tmp[c], sizes[c] = tmp[n_host + c], bases[c] = tmp[2 * n_host + c];
-    } else {
-      SBX_HIP(h, hipMemcpyAsync(roots.data(), info, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
-      SBX_HIP(h, hipMemcpyAsync(sizes.data(), info + n_host, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
-      SBX_HIP(h, hipMemcpyAsync(bases.data(), info + 2 * (size_t)n_host, n_host * sizeof(I), hipMemcpyDeviceToHost, h->stream));
-      SBX_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    }
-    // the pre-swept component goes first: its sweep state (q, ppos) is still live
-    for (unsigned c = 1; c < n_host; c++)
-      if (first_is_large && roots[c] == v0) {
-        std::swap(roots[c], roots[0]);
-        std::swap(sizes[c], sizes[0]);
-        std::swap(bases[c], bases[0]);
-      }
-    for (unsigned c = 0; c < n_host; c++) {
-      // pseudo-peripheral search from the component's smallest vertex (:22-81)
-      //
-      // The search ends with the first candidate root whose sweep does not deepen the level
-      // structure, and the Cuthill-McKee sweep that follows starts from that same vertex: the
-      // two sweeps discover identical levels and differ only in the order inside a level.  So
-      // from the third candidate on (the usual place for the search to end) the Cuthill-McKee
-      // sweep is run FIRST.  If the structure did not deepen it already is the final sweep —
-      // one sweep saved; if it did, the plain sweep is still needed (its order inside the last
-      // level breaks the ties for the next candidate) and the speculative one was wasted.
-      // Either way the output is the reference's; only the number of sweeps differs.
-      Searched sd;
-      if (c == 0 && comp0_searched) sd = sd0;
-      else SBX_TRY(search_component(roots[c], sizes[c], first_is_large && roots[c] == v0, sd));
-      const BfsResult &r = sd.r;
-      const int64_t sweeps = sd.sweeps, levels = sd.levels, candidate = sd.candidate;
-      const bool cm_done = sd.cm_done;
-      if (!(c == 0 && comp0_searched)) {
-        SBX_KLAUNCH(h, SBX_K_RCM_MISC, k_write_component, dim3(sbx_grid_for(r.count, 256, 4096)), dim3(256),
-                           (const I *)q, r.count, bases[c], inv, (const I *)nullptr);
-        SBX_LAUNCH_CHECK(h);
-      }
-      // invariant of the sweeps (k_visited_from_ppos relies on it): ppos is UNSEEN outside the running sweep
-      if (c + 1 < n_host) SBX_TRY(reset_ppos(h, (const I *)q, r.count, ppos, n));
-      if (sizes[c] > largest) {
-        largest = sizes[c];
-        sweeps_max = sweeps;
-        levels_max = levels;
-        // what the reference's serial algorithm runs on this component: its pseudo-peripheral sweeps (a speculative
-        // Cuthill-McKee sweep that ended the search stood in for the last of them) + the Cuthill-McKee sweep
-        ref_sweeps_max = candidate + (cm_done ? 1 : 0) + 1;
-      }
-    }
-  }
-  SBX_TRY(join_ranks());  // inputs without a large component never ran a Cuthill-McKee sweep
-  RcmDev fin;  // (also the synchronisation point of the call)
-  if (comp0_searched && n_host == 1 && !mid_batched) fin = hd;  // nothing was launched behind that read-back
-  else SBX_TRY(sbx_readback(h, &fin, dv, sizeof(RcmDev)));
-  if (fin.unsym)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG,
-             "sbx_rcm_reorder: the pattern is not structurally symmetric (a BFS cannot reach its whole component); "
-             "RCM is defined on symmetric patterns");
-  if (stats_host) {
-    stats_host->small_components = hd.n_small + (mid_batched ? hd.n_mid : 0u);
-    stats_host->large_components = n_host;
-    stats_host->bfs_sweeps = sweeps_max;
-    stats_host->bfs_levels = levels_max;
-    stats_host->edges_scanned = (int64_t)(fin.edges + fin.edges_bu);  // (a bottom-up kernel counts in edges_bu alone)
-    stats_host->edges_scanned_bottom_up = (int64_t)fin.edges_bu;
-    stats_host->largest_component = largest;
-    stats_host->components = (int64_t)hd.n_components;
-    stats_host->isolated = (int64_t)hd.n_empty_rows;
-    stats_host->reference_sweeps = ref_sweeps_max;
-    stats_host->unordered_sweeps = unordered_sweeps;
-  }
-  return SBX_OK;
+  RcmCall c;
+  c.h = h;
+  c.rp = (const X *)row_ptr, c.col = (const X *)col_v, c.inv = (X *)inv_perm_out;
+  c.n = n, c.nnz = nnz;
+  SBX_TRY(alloc_buffers(h, c));
+  SBX_TRY(degree_counts(h, c));
+  SBX_TRY(first_sweep(h, c));
+  SBX_TRY(label_rest(h, c));  // (with the first component's search beside it where that pays: search_component)
+  SBX_TRY(order_small_components(h, c));
+  SBX_TRY(order_host_components(h, c));
+  return finish(h, c, stats_host);
 }
