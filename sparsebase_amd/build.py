@@ -36,6 +36,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbfx.h"))
     hs.append(os.path.join(ROOT, "include", "sbsym.h"))
     hs.append(os.path.join(ROOT, "include", "sbmv.h"))
+    hs.append(os.path.join(ROOT, "include", "sbmm.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

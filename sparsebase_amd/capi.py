@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h, include/sbfx.h, include/sbsym.h and include/sbmv.h
+include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h and include/sbmm.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -196,6 +196,12 @@ MV_PROTOTYPES = {
     "sbmv_csr_spmv": ([_H, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int),
 }
 
+# every symbol include/sbmm.h declares (tests/test_mm_abi.py checks header <-> library <-> this table): the CSR times
+# dense block product, prefix `sbmm_`
+MM_PROTOTYPES = {
+    "sbmm_csr_spmm": ([_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
+}
+
 _lib = None
 
 
@@ -211,7 +217,7 @@ def load():
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
                                            list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items()) +
-                                           list(MV_PROTOTYPES.items())):
+                                           list(MV_PROTOTYPES.items()) + list(MM_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -293,7 +293,43 @@ __device__ __forceinline__ void sbx_load_items8(const I *__restrict__ col, int64
   }
 }
 
+// a thread's 8 consecutive values [base, base + 8) of a tile ending at t1, as sbx_load_items8 loads its columns (4- and
+// 8-byte value types of the products)
+template <typename V>
+__device__ __forceinline__ void sbx_load_values8(const V *__restrict__ a, int64_t base, int64_t t1, bool vec_ok, V *v) {
+  constexpr int ITEMS = 8;
+  if (vec_ok && base + ITEMS <= t1) {
+    if constexpr (sizeof(V) == 4) {
+      const uint4 q0 = *(const uint4 *)(a + base), q1 = *(const uint4 *)(a + base + 4);
+      const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+      for (int k = 0; k < ITEMS; k++) v[k] = __builtin_bit_cast(V, w[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < ITEMS; k += 2) {
+        const ulonglong2 q = *(const ulonglong2 *)(a + base + k);
+        v[k] = __builtin_bit_cast(V, (uint64_t)q.x);
+        v[k + 1] = __builtin_bit_cast(V, (uint64_t)q.y);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) v[k] = a[base + k < t1 ? base + k : t1 - 1];
+  }
+}
+
 namespace {  // (a kernel in a header shared by several translation units: internal linkage)
+
+// first[t] = the last row r in [0, n - 1] with rp[r] <= t * TILE, one thread per tile of TILE stored entries (the search
+// in row_ptr a workgroup would otherwise do for itself); first[tiles] = n - 1.  64-bit rows, and every row lies in
+// [0, n - 1] whatever rp holds: the spans of the products (sbx_spmv.hip, sbx_spmm.hip).
+template <typename N, int TILE, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_tile_first_rows(const N *__restrict__ rp, int64_t n, int64_t tiles,
+                                                             int64_t *__restrict__ first) {
+  const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (t > tiles) return;
+  first[t] = t == tiles ? n - 1 : sbx_row_of(rp, n, t * TILE);
+}
 
 // first and last row of every TILE-wide tile of the nonzeros, one thread per tile: the two searches in row_ptr are four
 // dependent rounds of loads when a workgroup does them for itself, and 25 waves of workgroups per CU then spend half

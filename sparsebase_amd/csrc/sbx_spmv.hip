@@ -30,7 +30,7 @@ namespace {
 
 constexpr int MV = 256;                  // threads per workgroup
 constexpr int MV_TILE = MV * MV_ITEMS;   // entries per tile: 2048
-static_assert(MV_ITEMS == 8, "sbx_load_items8 and mv_load8 load eight entries");
+static_assert(MV_ITEMS == 8, "sbx_load_items8 and sbx_load_values8 load eight entries");
 
 // ---- sbmv_csr_check ------------------------------------------------------------------------------------------------
 struct alignas(128) MvCheck {
@@ -62,15 +62,6 @@ __global__ __launch_bounds__(MV) void k_mv_check(const N *__restrict__ rp, const
 }
 
 // ---- sbmv_csr_spmv -------------------------------------------------------------------------------------------------
-// first[t] = the last row r in [0, n - 1] with rp[r] <= t * MV_TILE; first[tiles] = n - 1
-template <typename N>
-__global__ __launch_bounds__(MV) void k_mv_spans(const N *__restrict__ rp, int64_t n, int64_t tiles,
-                                                 int64_t *__restrict__ first) {
-  const int64_t t = (int64_t)blockIdx.x * MV + threadIdx.x;
-  if (t > tiles) return;
-  first[t] = t == tiles ? n - 1 : sbx_row_of(rp, n, t * MV_TILE);
-}
-
 // the last row r in [ra, rb] with rp[r] <= p, given ra <= rb; a row_ptr that is not ascending gives some row of [ra, rb]
 template <typename N>
 __device__ __forceinline__ int64_t mv_row_of(const N *__restrict__ rp, int64_t p, int64_t ra, int64_t rb) {
@@ -81,29 +72,6 @@ __device__ __forceinline__ int64_t mv_row_of(const N *__restrict__ rp, int64_t p
     if ((int64_t)rp[mid] <= p) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// a thread's 8 consecutive values [base, base + 8) of a tile ending at t1, as sbx_load_items8 loads its columns
-template <typename V>
-__device__ __forceinline__ void mv_load8(const V *__restrict__ a, int64_t base, int64_t t1, bool vec_ok, V *v) {
-  if (vec_ok && base + MV_ITEMS <= t1) {
-    if constexpr (sizeof(V) == 4) {
-      const uint4 q0 = *(const uint4 *)(a + base), q1 = *(const uint4 *)(a + base + 4);
-      const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-      for (int k = 0; k < MV_ITEMS; k++) v[k] = __builtin_bit_cast(V, w[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < MV_ITEMS; k += 2) {
-        const ulonglong2 q = *(const ulonglong2 *)(a + base + k);
-        v[k] = __builtin_bit_cast(V, (uint64_t)q.x);
-        v[k + 1] = __builtin_bit_cast(V, (uint64_t)q.y);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < MV_ITEMS; k++) v[k] = a[base + k < t1 ? base + k : t1 - 1];
-  }
 }
 
 template <typename I, typename N, typename V>
@@ -126,7 +94,7 @@ __global__ __launch_bounds__(MV) void k_spmv_tile(const N *__restrict__ rp, cons
   V v[MV_ITEMS], prod[MV_ITEMS];
   sbx_load_items8(col, base, t1, col_vec, c);
   if (val) {
-    mv_load8(val, base, t1, val_vec, v);
+    sbx_load_values8(val, base, t1, val_vec, v);
   } else {
 #pragma unroll
     for (int k = 0; k < MV_ITEMS; k++) v[k] = (V)1;
@@ -250,7 +218,7 @@ static int mv_spmv(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
   SBX_TRY(sbx_salloc(h, (size_t)tiles, &trow));
   SBX_TRY(sbx_salloc(h, (size_t)tiles, &tsum));
   const unsigned gt = (unsigned)((tiles + 1 + MV - 1) / MV);
-  SBX_KLAUNCH(h, SBX_K_SPMV, (k_mv_spans<N>), dim3(gt), dim3(MV), (const N *)row_ptr, n, tiles, first);
+  SBX_KLAUNCH(h, SBX_K_SPMV, (k_tile_first_rows<N, MV_TILE, MV>), dim3(gt), dim3(MV), (const N *)row_ptr, n, tiles, first);
   SBX_KLAUNCH(h, SBX_K_SPMV, (k_spmv_tile<I, N, V>), dim3((unsigned)tiles), dim3(MV), (const N *)row_ptr, (const I *)col,
               (const V *)val, (const V *)x, m, nnz, (const int64_t *)first, ((uintptr_t)col & 15) == 0,
               ((uintptr_t)val & 15) == 0, (V *)y, trow, tsum);

@@ -1,4 +1,4 @@
-// Loaders, preprocess functions and the SpMV kernel function for experiment::ConcreteExperiment (reference:
+// Loaders, preprocess functions and the SpMV and SpMM kernel functions for experiment::ConcreteExperiment (reference:
 // experiment/experiment_helper.h:21-124 for LoadFormat ... Reorder; the rest is this project's own).
 //
 //   LoadFormat / LoadCSR / LoadCOO / LoadCSC   file_names[0] through ReaderType into data["format"]
@@ -6,6 +6,7 @@
 //   LoadHIPCSR / ReorderHIP                    the device-resident twins: an HIPCSR on device SBX_DEVICE in and out, so that
 //                                              no kernel call of the canonical pipeline pays a trip over PCIe
 //   SpMV<I, N, V, F>                           the KernelFunction: y = A x on the device (kernels/spmv.h)
+//   SpMM<I, N, V, F>                           the KernelFunction: Y = A X for k columns on the device (kernels/spmm.h)
 //
 // As in the reference, the ContextType of ReorderCSR and Reorder is default-constructed: that is CPUContext, whose
 // formats the host layer stages through the device as it does everywhere.
@@ -22,6 +23,7 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/kernels/spmm.h"
 #include "sparsebase/kernels/spmv.h"
 
 namespace sparsebase::experiment {
@@ -102,6 +104,17 @@ void ReorderHIP(DataMap &data, std::any fparams, std::any params) {
   data["processed_format"] = bases::ReorderBase::Permute2D<format::HIPCSR>(perm.get(), A, {&gpu}, true);
 }
 
+namespace detail {
+// a kernel function's array parameter on the device: an HIPArray is borrowed, a host Array staged
+template <typename FloatType>
+kernels::detail::DeviceVector<FloatType> OperandOf(std::any &param, const hip::Device &dev, const char *who, const char *what) {
+  if (auto *d = std::any_cast<format::HIPArray<FloatType>>(&param))
+    return kernels::detail::DeviceVector<FloatType>::Borrow(d, dev, what);
+  if (auto *h = std::any_cast<format::Array<FloatType>>(&param)) return kernels::detail::DeviceVector<FloatType>::Stage(h, dev);
+  throw utils::TypeException(std::string(who) + what + " must be an Array or an HIPArray of the kernel's FloatType");
+}
+}  // namespace detail
+
 // The SpMV KernelFunction, with the contract of the reference example's kernels
 // (examples/example_experiment/example_experiment.cu:32-55): data["processed_format"] is a CSR or an HIPCSR of
 // <IDType, NNZType, ValueType>; fparams holds x as an Array<FloatType> or an HIPArray<FloatType>; kparams holds the values
@@ -115,10 +128,7 @@ std::any SpMV(DataMap &data, std::any &fparams, std::any &pparams, std::any &kpa
   format::Format *A = data.at("processed_format");
   const bool resident = A->template IsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>();
   auto vector_of = [](std::any &param, const hip::Device &dev, const char *what) {
-    if (auto *d = std::any_cast<format::HIPArray<FloatType>>(&param))
-      return kernels::detail::DeviceVector<FloatType>::Borrow(d, dev, what);
-    if (auto *h = std::any_cast<format::Array<FloatType>>(&param)) return kernels::detail::DeviceVector<FloatType>::Stage(h, dev);
-    throw utils::TypeException(std::string("experiment::SpMV: ") + what + " must be an Array or an HIPArray of the kernel's FloatType");
+    return detail::OperandOf<FloatType>(param, dev, "experiment::SpMV: ", what);
   };
   const bool own_vals = !kparams.has_value() && std::is_same_v<ValueType, FloatType>;
   View v = resident ? View::Borrow(A->template AsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>())
@@ -131,6 +141,46 @@ std::any SpMV(DataMap &data, std::any &fparams, std::any &pparams, std::any &kpa
   hip::Staged<FloatType> d_y(*v.dev, n ? n : 1);
   kernels::detail::Multiply(v, x, kparams.has_value() ? &vals : nullptr, d_y.get());
   FloatType *y = new FloatType[n ? n : 1];
+  try {
+    d_y.ToHost(y);  // (a blocking copy behind the kernels on the handle's stream: the synchronise)
+  } catch (...) {
+    delete[] y;
+    throw;
+  }
+  return y;
+}
+
+// The kernel parameter of SpMM: the number of columns of X and, optionally, the values (an Array<FloatType> or an
+// HIPArray<FloatType>; empty: the matrix's own values where ValueType is FloatType, else a pattern).
+struct SpMMParams {
+  size_t k = 1;
+  std::any vals;
+};
+
+// The SpMM KernelFunction, with SpMV's contract: data["processed_format"] is a CSR or an HIPCSR of <IDType, NNZType,
+// ValueType>; fparams holds X, m * k values row-major, as an Array<FloatType> or an HIPArray<FloatType>; kparams holds an
+// SpMMParams.  The result is a host FloatType* of n * k values from new[], owned by the caller, returned after the device
+// has finished.  Host data is staged on every call, inside the harness's timing; device-resident data pays the download of
+// Y alone.
+template <typename IDType, typename NNZType, typename ValueType, typename FloatType>
+std::any SpMM(DataMap &data, std::any &fparams, std::any &pparams, std::any &kparams) {
+  typedef reorder::detail::DeviceCsrView<IDType, NNZType, ValueType> View;
+  auto *params = std::any_cast<SpMMParams>(&kparams);
+  if (!params) throw utils::TypeException("experiment::SpMM: the kernel's parameter must be an SpMMParams");
+  format::Format *A = data.at("processed_format");
+  const bool resident = A->template IsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>();
+  const bool has_vals = params->vals.has_value();
+  const bool own_vals = !has_vals && std::is_same_v<ValueType, FloatType>;
+  View v = resident ? View::Borrow(A->template AsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>())
+                    : View::Stage(A->template AsAbsolute<format::CSR<IDType, NNZType, ValueType>>(), own_vals);
+  utils::detail::CsrViewGuard<IDType, NNZType, ValueType> guard{v};
+  auto x = detail::OperandOf<FloatType>(fparams, *v.dev, "experiment::SpMM: ", "X (the file's parameter)");
+  kernels::detail::DeviceVector<FloatType> vals;
+  if (has_vals) vals = detail::OperandOf<FloatType>(params->vals, *v.dev, "experiment::SpMM: ", "the values (the kernel's parameter)");
+  const size_t count = (size_t)v.n * params->k;
+  hip::Staged<FloatType> d_y(*v.dev, count ? count : 1);
+  kernels::detail::MultiplyBlock(v, x, params->k, has_vals ? &vals : nullptr, d_y.get());
+  FloatType *y = new FloatType[count ? count : 1];
   try {
     d_y.ToHost(y);  // (a blocking copy behind the kernels on the handle's stream: the synchronise)
   } catch (...) {

@@ -1,4 +1,4 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h, sbmm.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -479,6 +479,46 @@ def csr_spmv(row_ptr, col, x, val=None, m=None, out=None):
         raise TypeError("out must have the dtype of x and one value per row")
     hd.check(hd.lib.sbmv_csr_spmv(hd.h, _it(row_ptr, col), _vt(x), n, m, col.numel(), _p(row_ptr), _p(col), _p(val), _p(x),
                                   _p(y)))
+    return y
+
+
+# ----------------------------------------------------------------------------- Y = A X (include/sbmm.h)
+def _check_rows(t, what):
+    """A 2-D device tensor whose rows are contiguous (stride(1) == 1, any leading dimension at least its width)."""
+    if not t.is_cuda:
+        raise ValueError("sparsebase_amd.ops works on device tensors only (no CPU path)")
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what} must be 2-D with stride(1) == 1 and stride(0) >= its width")
+
+
+def _ld(t):
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def csr_spmm(row_ptr, col, X, val=None, m=None, out=None):
+    """Y = A X of a CSR matrix and a dense row-major block: a device tensor of n x k values of X's dtype (float32, float64,
+    int32 or int64; integers wrap).  X is 2-D with stride(1) == 1 (a column slice of a wider tensor is fine: its stride(0)
+    is the leading dimension), as is `out`.  val=None is a pattern matrix (every stored value 1); m defaults to
+    X.shape[0].  Deterministic and asynchronous; an entry whose column lies outside [0, m) contributes nothing; nothing is
+    written outside out[:, :k].  See sbmm_csr_spmm in include/sbmm.h."""
+    dev = _check_dev(row_ptr, col, val)
+    _check_rows(X, "X")
+    if out is not None:
+        _check_rows(out, "out")
+    if X.device != dev or (out is not None and out.device != dev):
+        raise ValueError("all tensors must live on the same device")
+    hd = handle_for(dev)
+    n, k = row_ptr.numel() - 1, int(X.shape[1])
+    m = int(X.shape[0]) if m is None else int(m)
+    if m > X.shape[0]:
+        raise ValueError(f"X holds {X.shape[0]} rows, the matrix has {m} columns")
+    if val is not None and (val.dtype != X.dtype or val.numel() != col.numel()):
+        raise TypeError("val must have the dtype of X and one value per stored entry")
+    y = torch.empty((n, k), dtype=X.dtype, device=X.device) if out is None else out
+    if y.dtype != X.dtype or tuple(y.shape) != (n, k):
+        raise TypeError("out must have the dtype of X, one row per row of the matrix and one column per column of X")
+    hd.check(hd.lib.sbmm_csr_spmm(hd.h, _it(row_ptr, col), _vt(X), n, m, col.numel(), k, _p(row_ptr), _p(col), _p(val),
+                                  _p(X), _ld(X), _p(y), _ld(y)))
     return y
 
 
