@@ -5,20 +5,27 @@
 //   A13 bases/reorder_base.h:663-672         sbx_inverse_permutation
 //       permute/permute_order_one.cc:18-37   sbx_permute_array
 //
-// Data flow of one permute (new rows [row_begin,row_end) — the multi-GPU shard):
-//   k_rowwise_prep  from the old-row side: rec[row_order[u]] = (length, source offset)   (12n B r, 8n B w)
-//   k_classify_scan lengths -> row_ptr_out (single-pass scan), the short rows' prefix sums, long rows listed by class
-//   no column map:  k_permute_copy, a segmented copy (+ in-row order check; unsorted input
-//                   rows redo the call through the sorting kernels below)
-//   column map:
-//   k_permute_tile  one workgroup per PT_W output nonzeros: gathers whole old rows (col relabelled
-//                   through col_order) and sorts every row of <= PT_LMAX entries in LDS with ONE
-//                   bucket-rank pass (below); streams them out.
-//   k_permute_block_rows  rows of PT_LMAX..8K entries: one workgroup per row in three capacity
-//                   classes, the same bucket-rank sort.
-//   long rows       longer rows: gathered into a compact buffer, sorted by
-//                   (row, col) with the device radix sort, scattered back.
-//   k_fix_dup_runs  only if some row was unsorted AND duplicate columns exist:
+// One permute (new rows [row_begin,row_end) — the multi-GPU shard), route by route; the host driver is at the end of
+// the file (PermCall, perm_prepare, sort_stage and its paths, the entry points):
+//   preparation     perm_prepare: k_rowwise_prep from the old-row side, rec[row_order[u]] = (length, source offset)
+//                   (12n B r, 8n B w); k_classify_reduce / _prefix / _scan: lengths -> row_ptr_out, the short rows' prefix
+//                   sums, the longer rows listed by class (and, for a relabelling permute, the tiles' first rows).
+//                   Beside it, when columns are relabelled: k_cdf_sample, k_cdf_table, the key-distribution map.
+//   no column map   rowwise_copy: k_tile_rows, k_permute_copy, a segmented copy with an in-row order check; unsorted
+//                   input rows are classified again there and redo the call through the sort stage below.
+//   sort stage      sort_stage, for the relabelling permute, csr_sort_rows and sbx_sort_segments:
+//     rows <= PT_LMAX      tile_rows_path: a wave per PT_W output nonzeros gathers whole old rows (columns relabelled
+//                          through col_order) and sorts them in LDS in one bucket-rank pass (below).  k_permute_tile2 with a
+//                          map; else k_permute_tile and, for the tiles whose columns cluster, k_permute_tile_radix.
+//     rows <= 8 K          block_rows_path: one workgroup per row in six capacity classes of 256 ... 8192 slots (five for
+//                          8-byte values), the same sort: k_rows_quad (sbx_rowsort.h) with a column map, except the 512-slot
+//                          class; else k_permute_block_rows.  Clustered rows: k_permute_rows_radix.
+//     longer rows          long_rows_path, with a column map: cut into segments by column range (k_long_seg_offsets,
+//                          _gather, _hist, _scan, _partition) that k_rows_quad sorts as virtual rows, k_permute_rows_radix
+//                          behind them.  Rows it declines and every long row of the other callers, long_rows_radix_path:
+//                          k_long_lengths, k_long_gather, the device radix sort on (row, column), k_long_scatter.
+//     m beyond 2^31        wide_rows_path: k_wide_gather, one radix sort of all entries, k_wide_scatter.
+//   k_fix_dup_runs  behind the stage; works only if some row was unsorted AND duplicate columns exist:
 //                   orders equal-column runs by value (std::less<pair<col,val>>).
 // HBM traffic per nonzero in the copy, tile and block paths is the compulsory 2*(I+V) bytes.
 //
@@ -34,6 +41,7 @@
 // is (column, original position): the sort is stable.  A bucket of more than BK_MAX entries (a row
 // whose columns cluster far more tightly than its range) sends the tile to the LSD radix sort kept
 // below as the distribution-independent path.
+#include <type_traits>
 #include "sbx_device.h"
 #include "sbx_internal.h"
 
@@ -1324,27 +1332,6 @@ __global__ __launch_bounds__(CDF_K) void k_cdf_table(const unsigned *__restrict_
   table[tid] = make_uint2((unsigned)b0, flat ? 0u : (unsigned)((b1 - b0) >> 16));
 }
 
-// enqueues the map's kernels on h->stream; map->table == nullptr afterwards: not applicable
-template <typename I>
-static int build_cdf_map(sbx_handle_t h, const I *col_in, const I *col_order, int64_t nnz, int64_t m, CdfMap *map) {
-  map->table = nullptr, map->shift = 0, map->fsh = 0;
-  const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
-  if (col_bits > CDF_MAX_COL_BITS || nnz <= 0 || !col_order) return SBX_OK;
-  unsigned *hist = nullptr;
-  uint2 *table = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)CDF_K, &hist));
-  SBX_TRY(sbx_salloc(h, (size_t)CDF_K, &table));
-  SBX_HIP(h, hipMemsetAsync(hist, 0, sizeof(unsigned) * CDF_K, h->stream));
-  const int shift = col_bits > CDF_LOG_K ? col_bits - CDF_LOG_K : 0;
-  const int64_t want = (nnz + 256 * CDF_SAMPLE_ITEMS - 1) / (256 * CDF_SAMPLE_ITEMS);
-  const unsigned blocks = (unsigned)(want < CDF_SAMPLE_BLOCKS ? want : CDF_SAMPLE_BLOCKS);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_cdf_sample<I>, dim3(blocks), dim3(256), col_in, col_order, nnz, m, shift, hist);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_cdf_table, dim3(1), dim3(CDF_K), (const unsigned *)hist, table, shift == 0 ? 1 : 0);
-  SBX_LAUNCH_CHECK(h);
-  map->table = table, map->shift = shift, map->fsh = shift ? 32 - shift : 0;
-  return SBX_OK;
-}
-
 #define PT2_RSRC_FLAGS 0x00020000  // raw buffer, 32-bit data format (gfx9 descriptor word 3)
 typedef unsigned pt2_u2 __attribute__((ext_vector_type(2)));
 
@@ -2473,15 +2460,52 @@ __global__ __launch_bounds__(256) void k_fix_dup_runs(const I *__restrict__ rpo,
   }
 }
 
+// ---- the host driver ------------------------------------------------------------------------------------------------
+// What every route of one call reads.  The entry fills the first block, perm_prepare() the second; the routes take the
+// context by reference plus only what is their own.
 template <typename I>
-int launch_fix(sbx_handle_t h, sbx_value_type vt, const I *rpo, const I *col, void *val, int64_t nr, PermState *st) {
-  const unsigned grid = sbx_grid_for(nr, 256, 4096);
+struct PermCall {
+  sbx_handle_t h;
+  sbx_value_type vt;  // decides the value ordering of duplicate columns (SBX_V_NONE: none)
+  int vb;             // bytes per value: 0 (pattern only), 4 or 8
+  const I *col_in;    // the source's columns and values (nnz_in entries), read through rec
+  const char *val_in;
+  const I *col_order;  // nullptr: columns keep their ids
+  const I *rpo;        // row_ptr of the output, nr + 1 entries
+  I *col_out;
+  char *val_out;
+  int64_t nr, m, total, nnz_in;  // output rows, columns, output entries, entries of col_in / val_in
+
+  int col_bits;     // bits of a column id
+  const int2 *rec;  // (length, source offset) per output row
+  I *sp;            // prefix sums of the rows the tile kernels sort
+  I *long_rows, *block_rows;  // the rows that do not fit a tile, by class (block_rows: BR_CLASSES lists, block_stride apart)
+  int64_t block_stride;
+  I *tile_first;    // first row of every tile, from the classification pass (nullptr: k_tile_first makes it)
+  PermState *st;    // on the device
+  PermState hs;     // ... and as perm_fetch() read it
+  CdfMap cdf;       // table == nullptr: no map
+  bool cdf_on_side;  // the map was built on side stream 1: the sort stage waits for aux_event[2]
+};
+
+// The one place where a value width in bytes becomes a template argument: f(std::integral_constant<int, 0 / 4 / 8>()).
+template <typename F>
+int with_value_bytes(int vb, F &&f) {
+  if (vb == 0) return f(std::integral_constant<int, 0>());
+  if (vb == 4) return f(std::integral_constant<int, 4>());
+  return f(std::integral_constant<int, 8>());
+}
+
+template <typename I>
+int launch_fix(const PermCall<I> &c) {
+  sbx_handle_t h = c.h;
+  const unsigned grid = sbx_grid_for(c.nr, 256, 4096);
 #define FIX(VT)                                                                                              \
   case VT:                                                                                                   \
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_fix_dup_runs<I, typename Typed<VT>::T>), dim3(grid), dim3(256), rpo, col, \
-                       (typename Typed<VT>::T *)val, nr, (const PermState *)st);                            \
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_fix_dup_runs<I, typename Typed<VT>::T>), dim3(grid), dim3(256), c.rpo, \
+                (const I *)c.col_out, (typename Typed<VT>::T *)c.val_out, c.nr, (const PermState *)c.st);     \
     break;
-  switch (vt) {
+  switch (c.vt) {
     FIX(SBX_V_I32) FIX(SBX_V_U32) FIX(SBX_V_F32) FIX(SBX_V_I64) FIX(SBX_V_U64) FIX(SBX_V_F64)
     default: return SBX_OK;
   }
@@ -2538,110 +2562,106 @@ constexpr int64_t TILE_GRID_FACTOR = SBX_PERMUTE_TILE_GRID < 1 ? 1 : SBX_PERMUTE
 #include "sbx_rowsort.h"
 
 
-// rows of PT_LMAX < length <= 8 K: one workgroup per row, by capacity class
+// ---- rows of PT_LMAX < length <= 8 K: one workgroup per row, by capacity class ---------------------------------------
+// One class of `rows` rows.  Its grid is persistent: enough workgroups to fill the CUs' LDS a few times over, each walking
+// its rows as a pipeline — min(by_lds, by_waves) resident workgroups per CU times PERMUTE_GRID_FACTOR, at most one per row.
+// The hand-over: `launch(grid)` enqueues on h->stream; a class with a side stream of its own (fork, and a CLASS_STREAMS
+// digit other than 0) waits there for the stage's fork event, and the stream it came from — side stream 0, where the
+// radix kernel joins the classes — waits for it.
+template <typename Launch>
+int run_class(sbx_handle_t h, int cls, bool fork, unsigned rows, unsigned by_lds, unsigned by_waves, Launch &&launch) {
+  if (!rows) return SBX_OK;
+  const unsigned per_cu = by_lds < by_waves ? by_lds : by_waves;
+  const unsigned fill = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * PERMUTE_GRID_FACTOR;
+  const unsigned grid = fill > rows ? rows : fill;
+  const int si = fork ? CLASS_STREAMS.s[cls] : 0;
+  if (!si) return launch(grid);
+  hipStream_t base = h->stream;
+  {
+    sbx_stream_scope on_side(h, h->aux_stream[si]);
+    SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[0], 0));
+    SBX_TRY(launch(grid));
+    SBX_HIP(h, hipEventRecord(h->aux_event[1 + si], h->stream));
+  }
+  SBX_HIP(h, hipStreamWaitEvent(base, h->aux_event[1 + si], 0));
+  return SBX_OK;
+}
+
+// k_permute_block_rows (round 3's kernel): class CLS with THREADS threads per row; fb_rows: where the kernels list the
+// rows whose columns cluster, for the radix kernel behind them
+template <int VB, int CLS, int THREADS, typename I>
+int block_rows(const PermCall<I> &c, bool fork, unsigned *fb_rows) {
+  // resident workgroups per CU: LDS (12 B per slot) and ~24 waves (the kernels need 64..100 VGPRs)
+  const unsigned rows = c.hs.n_block[CLS], by_lds = 160 * 1024 / (br_cap(CLS) * 12 + 256), by_waves = 24 / (THREADS / 64);
+  return run_class(c.h, CLS, fork, rows, by_lds, by_waves, [&](unsigned grid) -> int {
+    SBX_KLAUNCH(c.h, SBX_K_PERMUTE_BLOCK, (k_permute_block_rows<I, VB, br_cap(CLS), THREADS>), dim3(grid), dim3(THREADS),
+                c.rec, c.col_in, c.val_in, c.col_order, c.rpo, (const I *)c.block_rows + CLS * c.block_stride, (int)rows,
+                c.col_out, c.val_out, c.st, (int)sbx_sw().permute_force_radix, fb_rows, &c.st->n_fb_rows,
+                (const unsigned *)nullptr);
+    return SBX_OK;
+  });
+}
+
+// k_rows_quad (needs a column map): THREADS threads x QUADS quads = the class capacity, compiled for MINW waves per SIMD
+template <int VB, int CLS, int THREADS, int QUADS, int MINW, typename I>
+int quad_rows(const PermCall<I> &c, bool fork, unsigned *fb_rows) {
+  static_assert(4 * THREADS * QUADS == br_cap(CLS), "class capacity");
+  const unsigned rows = c.hs.n_block[CLS], by_lds = 160 * 1024 / RqLds<VB, THREADS, QUADS>::BYTES;
+  const unsigned by_waves = (THREADS >= 512 ? 16 : RQ_WAVES_PER_CU) / (THREADS / 64);
+  return run_class(c.h, CLS, fork, rows, by_lds, by_waves, [&](unsigned grid) -> int {
+    SBX_KLAUNCH(c.h, SBX_K_PERMUTE_BLOCK, (k_rows_quad<I, VB, THREADS, QUADS, MINW>), dim3(grid), dim3(THREADS), c.rec,
+                c.col_in, c.val_in, c.col_order, c.rpo, (const I *)c.block_rows + CLS * c.block_stride, (int)rows,
+                c.col_out, c.val_out, c.st, (int)sbx_sw().permute_force_radix | PERMUTE_ABLATE, fb_rows, &c.st->n_fb_rows,
+                (const unsigned *)nullptr, (unsigned)((uint64_t)c.m * sizeof(I)));
+    return SBX_OK;
+  });
+}
+
 template <typename I, int VB>
-int block_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char *val_in, const I *col_order,
-                    const I *rpo, I *col_out, char *val_out, int64_t m, const I *block_rows,
-                    const unsigned *n_block, int64_t block_stride, int64_t block_nnz, PermState *st, bool fork) {
+int block_rows_path(const PermCall<I> &c, bool fork) {
   // fork: h->stream is side stream 0, which already waits for the fork event; the classes spread over side streams
   // 0, 2, 3, ... (1 belongs to the long rows) and the radix kernel behind them joins them again on stream 0
-  hipStream_t base = h->stream;
-  const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
-  const int force = sbx_sw().permute_force_radix;
+  sbx_handle_t h = c.h;
   size_t n_all = 0;
-  for (int c = 0; c < BR_CLASSES; c++) n_all += n_block[c];
+  for (int cls = 0; cls < BR_CLASSES; cls++) n_all += c.hs.n_block[cls];
   unsigned *fb_rows = nullptr;  // rows whose columns cluster (listed by the class kernels, sorted by the radix kernel)
   SBX_TRY(sbx_salloc(h, n_all + 1, &fb_rows));
-  // persistent grids: enough workgroups to fill the CUs' LDS a few times over, each walking its rows as a pipeline
-#define BLOCK_ROWS(CLS, THREADS)                                                                                  \
-  if (n_block[CLS]) {                                                                                             \
-    /* resident workgroups per CU: LDS (12 B per slot) and ~24 waves (the kernels need 64..100 VGPRs) */          \
-    const unsigned by_lds = (unsigned)(160 * 1024 / (br_cap(CLS) * 12 + 256)), by_waves = 24u / ((THREADS) / 64); \
-    const unsigned per_cu = by_lds < by_waves ? by_lds : by_waves;                                                \
-    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * PERMUTE_GRID_FACTOR;                       \
-    if (grid > n_block[CLS]) grid = n_block[CLS];                                                                 \
-    const int si = CLASS_STREAMS.s[CLS];                                                                          \
-    if (fork && si) {                                                                                             \
-      h->stream = h->aux_stream[si];                                                                              \
-      SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[0], 0));                                              \
-    }                                                                                                             \
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_BLOCK, (k_permute_block_rows<I, VB, br_cap(CLS), THREADS>), dim3(grid),          \
-                dim3(THREADS), rec, col_in, val_in, col_order, rpo, block_rows + (CLS)*block_stride,              \
-                (int)n_block[CLS], col_out, val_out, st, force, fb_rows, &st->n_fb_rows,                          \
-                (const unsigned *)nullptr);                                                                       \
-    if (fork && si) {                                                                                             \
-      const hipError_t e1_ = hipEventRecord(h->aux_event[1 + si], h->stream);                                     \
-      const hipError_t e2_ = hipStreamWaitEvent(base, h->aux_event[1 + si], 0);                                   \
-      h->stream = base;                                                                                           \
-      if (e1_ != hipSuccess || e2_ != hipSuccess) SBX_FAIL(h, SBX_ERR_HIP, "side stream hand-over failed");       \
-    }                                                                                                             \
-  }
-  // k_rows_quad: T threads x Q quads = the class capacity; the column map must fit a buffer descriptor (4 GB)
+  // k_rows_quad: the column map must fit a buffer descriptor (4 GB)
   // (without a column map — csr_sort_rows, the hybrid COO sort's groups — there is no gather to hide the sort behind and
   // round 3's kernels, lighter in registers, measure 6 % better on C2B: 0.536 against 0.570 ms)
   // (64-bit index arrays: the same kernel, two 16-byte accesses per quad of columns, the map's low words gathered)
-  const bool quad = col_order && (uint64_t)m * sizeof(I) <= 0xFFFFFFFCull;
-  const unsigned table_bytes = col_order ? (unsigned)((uint64_t)m * sizeof(I)) : 0u;
-#define QUAD_ROWS(CLS, THREADS, QUADS, MINW)                                                                      \
-  if (n_block[CLS]) {                                                                                             \
-    static_assert(4 * (THREADS) * (QUADS) == br_cap(CLS), "class capacity");                                      \
-    const unsigned by_lds = (unsigned)(160 * 1024 / RqLds<VB, THREADS, QUADS>::BYTES);                            \
-    const unsigned by_waves = (unsigned)((THREADS) >= 512 ? 16 : RQ_WAVES_PER_CU) / ((THREADS) / 64);             \
-    const unsigned per_cu = by_lds < by_waves ? by_lds : by_waves;                                                \
-    unsigned grid = (unsigned)h->num_cus * (per_cu < 1 ? 1 : per_cu) * PERMUTE_GRID_FACTOR;                       \
-    if (grid > n_block[CLS]) grid = n_block[CLS];                                                                 \
-    const int si = CLASS_STREAMS.s[CLS];                                                                          \
-    if (fork && si) {                                                                                             \
-      h->stream = h->aux_stream[si];                                                                              \
-      SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[0], 0));                                              \
-    }                                                                                                             \
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_BLOCK, (k_rows_quad<I, VB, THREADS, QUADS, MINW>), dim3(grid), dim3(THREADS), rec, \
-                col_in, val_in, col_order, rpo, block_rows + (CLS)*block_stride, (int)n_block[CLS], col_out,      \
-                val_out, st, force | PERMUTE_ABLATE, fb_rows, &st->n_fb_rows, (const unsigned *)nullptr,           \
-                table_bytes);                                                                                     \
-    if (fork && si) {                                                                                             \
-      const hipError_t e1_ = hipEventRecord(h->aux_event[1 + si], h->stream);                                     \
-      const hipError_t e2_ = hipStreamWaitEvent(base, h->aux_event[1 + si], 0);                                   \
-      h->stream = base;                                                                                           \
-      if (e1_ != hipSuccess || e2_ != hipSuccess) SBX_FAIL(h, SBX_ERR_HIP, "side stream hand-over failed");       \
-    }                                                                                                             \
-  }
-  if (quad) {
-    QUAD_ROWS(0, 64, 1, 1);
+  if (c.col_order && (uint64_t)c.m * sizeof(I) <= 0xFFFFFFFCull) {
+    SBX_TRY((quad_rows<VB, 0, 64, 1, 1>(c, fork, fb_rows)));
     // the 512-slot class keeps round 3's kernel: one wave per row and two quad steps need 112 registers (16 waves per
     // CU) where that kernel runs 24 waves — with the RCM order, whose rows all take the second sort level, 146 us against
     // its 118 on the bench matrix (random order: 128 / 112; measured again with the interleaved gathers of round 5: level)
-    BLOCK_ROWS(1, 64);
-    QUAD_ROWS(2, 128, 2, (sizeof(I) == 8 ? 4 : 1));  // (64-bit index arrays: held to 128 registers, four waves per SIMD)
-    QUAD_ROWS(3, 256, 2, (sizeof(I) == 8 ? 4 : 1));
-    QUAD_ROWS(4, 512, 2, (VB == 8 ? 2 : 4));  // two workgroups per CU: at most 128 registers (8-byte values: LDS allows one)
-    if constexpr (VB != 8) QUAD_ROWS(5, 1024, 2, 1);
-  }
-  if (!quad) {
+    SBX_TRY((block_rows<VB, 1, 64>(c, fork, fb_rows)));
+    SBX_TRY((quad_rows<VB, 2, 128, 2, (sizeof(I) == 8 ? 4 : 1)>(c, fork, fb_rows)));  // (64-bit index arrays: held to 128 registers, four waves per SIMD)
+    SBX_TRY((quad_rows<VB, 3, 256, 2, (sizeof(I) == 8 ? 4 : 1)>(c, fork, fb_rows)));
+    SBX_TRY((quad_rows<VB, 4, 512, 2, (VB == 8 ? 2 : 4)>(c, fork, fb_rows)));  // two workgroups per CU: at most 128 registers (8-byte values: LDS allows one)
+    if constexpr (VB != 8) SBX_TRY((quad_rows<VB, 5, 1024, 2, 1>(c, fork, fb_rows)));
+  } else {
     // threads per class, measured on the bench matrix: one wave (no s_barrier at all) up to 512 entries, 8 entries per
     // thread up to 2048, 4 for 4096 (8 per thread there: +5 %)
-    BLOCK_ROWS(0, 64);
-    BLOCK_ROWS(1, 64);
-    BLOCK_ROWS(2, 128);
-    BLOCK_ROWS(3, 256);
-    BLOCK_ROWS(4, 1024);
-    if constexpr (VB != 8) BLOCK_ROWS(5, 1024);  // 8-byte values: 8192 entries do not fit LDS, those rows are "long"
+    SBX_TRY((block_rows<VB, 0, 64>(c, fork, fb_rows)));
+    SBX_TRY((block_rows<VB, 1, 64>(c, fork, fb_rows)));
+    SBX_TRY((block_rows<VB, 2, 128>(c, fork, fb_rows)));
+    SBX_TRY((block_rows<VB, 3, 256>(c, fork, fb_rows)));
+    SBX_TRY((block_rows<VB, 4, 1024>(c, fork, fb_rows)));
+    if constexpr (VB != 8) SBX_TRY((block_rows<VB, 5, 1024>(c, fork, fb_rows)));  // 8-byte values: 8192 entries do not fit LDS, those rows are "long"
   }
-#undef BLOCK_ROWS
-#undef QUAD_ROWS
   SBX_KLAUNCH(h, SBX_K_PERMUTE_BLOCK, (k_permute_rows_radix<I, VB>), dim3((unsigned)(n_all < 512 ? n_all : 512)),
-              dim3(1024), rec, col_in, val_in, col_order, rpo, (const unsigned *)fb_rows, col_out, val_out, col_bits, st,
-              (const unsigned *)&st->n_fb_rows);
+              dim3(1024), c.rec, c.col_in, c.val_in, c.col_order, c.rpo, (const unsigned *)fb_rows, c.col_out, c.val_out,
+              c.col_bits, c.st, (const unsigned *)&c.st->n_fb_rows);
   SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_PERMUTE_BLOCK, block_nnz * (int64_t)(2 * (sizeof(I) + VB)));
+  SBX_PROF_BYTES(h, SBX_K_PERMUTE_BLOCK, (int64_t)c.hs.block_nnz * (int64_t)(2 * (sizeof(I) + VB)));
   return SBX_OK;
 }
 
 // longer rows: flat gather, device radix sort on (row rank, column), scatter back
 template <typename I, int VB>
-int long_rows_radix_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char *val_in, const I *col_order,
-                   const I *rpo, I *col_out, char *val_out, int64_t m, const I *long_rows,
-                   unsigned n_long, int64_t long_nnz, PermState *st) {
+int long_rows_radix_path(const PermCall<I> &c, const I *long_rows, unsigned n_long, int64_t long_nnz) {
+  sbx_handle_t h = c.h;
   uint32_t *loff = nullptr;
   uint64_t *ka = nullptr, *kb = nullptr;
   char *pa = nullptr, *pb = nullptr;
@@ -2652,38 +2672,36 @@ int long_rows_radix_path(sbx_handle_t h, const int2 *rec, const I *col_in, const
     SBX_TRY(sbx_salloc(h, (size_t)long_nnz * VB, &pa));
     SBX_TRY(sbx_salloc(h, (size_t)long_nnz * VB, &pb));
   }
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_lengths<I>, dim3((n_long + 255) / 256), dim3(256), rpo, long_rows, loff,
-                     (int)n_long);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_lengths<I>, dim3((n_long + 255) / 256), dim3(256), c.rpo, long_rows, loff,
+              (int)n_long);
   SBX_TRY(sbx_exclusive_scan_u32(h, loff, loff, n_long, nullptr));
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_gather<I, VB>), dim3(sbx_grid_for(long_nnz, 256, 8192)), dim3(256), rec,
-                     col_in, val_in, col_order, long_rows, (const uint32_t *)loff, (int)n_long, long_nnz, ka, pa, st);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_gather<I, VB>), dim3(sbx_grid_for(long_nnz, 256, 8192)), dim3(256), c.rec,
+              c.col_in, c.val_in, c.col_order, long_rows, (const uint32_t *)loff, (int)n_long, long_nnz, ka, pa, c.st);
   SBX_LAUNCH_CHECK(h);
   sbx_radix_pass passes[16];
-  const int np = sbx_radix_plan(0, sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0), 32,
-                                32 + sbx_bits_for((uint64_t)(n_long - 1)), passes);
+  const int np = sbx_radix_plan(0, c.col_bits, 32, 32 + sbx_bits_for((uint64_t)(n_long - 1)), passes);
   int in_b = 0;
   PermState hs2;  // rows that are already ordered (row-wise permutes) skip the sort
-  SBX_TRY(sbx_readback(h, &hs2, st, sizeof(PermState)));
+  SBX_TRY(sbx_readback(h, &hs2, c.st, sizeof(PermState)));
   if (hs2.long_unsorted) SBX_TRY(sbx_radix_sort(h, 8, VB, ka, kb, pa, pb, long_nnz, passes, np, &in_b));
   SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_scatter<I, VB>), dim3(sbx_grid_for(long_nnz, 256, 8192)), dim3(256),
-                     (const uint64_t *)(in_b ? kb : ka), (const char *)(in_b ? pb : pa), rpo, long_rows,
-                     (const uint32_t *)loff, long_nnz, col_out, val_out, st);
+              (const uint64_t *)(in_b ? kb : ka), (const char *)(in_b ? pb : pa), c.rpo, long_rows,
+              (const uint32_t *)loff, long_nnz, c.col_out, c.val_out, c.st);
   SBX_LAUNCH_CHECK(h);
   return SBX_OK;
 }
 
-
-
 // longer rows of a permute that relabels columns: segments sorted in LDS (kernels above); what that path declines
 // (rows already in order, overfull segments) and every long row of the other callers goes through the radix path
 template <typename I, int VB>
-int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char *val_in, const I *col_order,
-                   const I *rpo, I *col_out, char *val_out, int64_t m, const I *long_rows,
-                   unsigned n_long, int64_t long_nnz, PermState *st) {
-  if (!col_order || sbx_sw().permute_force_radix || long_nnz >= ((int64_t)1 << 31))
-    return long_rows_radix_path<I, VB>(h, rec, col_in, val_in, col_order, rpo, col_out, val_out, m, long_rows, n_long,
-                                    long_nnz, st);
-  const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
+int long_rows_path(const PermCall<I> &c) {
+  sbx_handle_t h = c.h;
+  const I *long_rows = c.long_rows;
+  PermState *st = c.st;
+  const unsigned n_long = c.hs.n_long;
+  const int64_t long_nnz = (int64_t)c.hs.long_nnz;
+  if (!c.col_order || sbx_sw().permute_force_radix || long_nnz >= ((int64_t)1 << 31))
+    return long_rows_radix_path<I, VB>(c, long_rows, n_long, long_nnz);
   const int seg_cap = BlockRowCap<VB>::value;
   const int target = seg_cap / 4;  // a segment: fewer than target + (one bin) entries
   const size_t seg_max = (size_t)(long_nnz / target) + (size_t)n_long + 2;  // sum of the rows' segment slots
@@ -2714,14 +2732,14 @@ int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char 
   SBX_TRY(sbx_salloc(h, (size_t)n_long, &fb_list));
   SBX_TRY(sbx_salloc(h, seg_max, &fb_rows));
   SBX_HIP(h, hipMemsetAsync(zero, 0, sizeof(unsigned) * zero_words, h->stream));
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_seg_offsets<I>, dim3(1), dim3(1024), rpo, long_rows, loff, foff, soff,
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_seg_offsets<I>, dim3(1), dim3(1024), c.rpo, long_rows, loff, foff, soff,
               (int)n_long, target);
   const unsigned chunks = (unsigned)((long_nnz + LS_CHUNK - 1) / LS_CHUNK);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_seg_gather<I, VB>), dim3(chunks), dim3(LS_THREADS), rec, col_in, val_in,
-              col_order, long_rows, (const uint32_t *)loff, (int)n_long, long_nnz, c1, v1, rowmm, row_unsorted, st);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_seg_gather<I, VB>), dim3(chunks), dim3(LS_THREADS), c.rec, c.col_in, c.val_in,
+              c.col_order, long_rows, (const uint32_t *)loff, (int)n_long, long_nnz, c1, v1, rowmm, row_unsorted, st);
   SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_seg_hist<I>, dim3(chunks), dim3(LS_THREADS), (const I *)c1,
               (const uint32_t *)loff, (const uint32_t *)foff, (int)n_long, long_nnz, (const unsigned *)rowmm, fine);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_seg_scan<I>, dim3(n_long), dim3(256), rpo, long_rows, (const uint32_t *)loff,
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, k_long_seg_scan<I>, dim3(n_long), dim3(256), c.rpo, long_rows, (const uint32_t *)loff,
               (const uint32_t *)foff, (const uint32_t *)soff, (int)n_long, long_nnz, target, seg_cap, fine, segstart,
               (const unsigned *)row_unsorted, row_skip, vrec, vrpo, vlist, (int64_t)seg_max, fb_list, st);
   SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_long_seg_partition<I, VB>), dim3(chunks), dim3(LS_THREADS), (const I *)c1,
@@ -2729,21 +2747,18 @@ int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char 
               long_nnz, target, (const unsigned *)rowmm, (const unsigned *)fine, (const unsigned *)segstart, cursor,
               (const unsigned *)row_skip, c2, v2);
   // the segments: virtual rows of the one-workgroup-per-row kernel (columns already relabelled: no column map)
-  {
-    // (512 threads, two workgroups per CU for segments of up to 4096 entries; 1024 threads for the longer ones)
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 512, 2, (VB == 8 ? 2 : 4)>), dim3(2 * (unsigned)h->num_cus), dim3(512),
-                (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo, (const I *)vlist,
-                0, col_out, val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows, (const unsigned *)&st->n_seg[0], 0u);
-    if constexpr (VB != 8) {
-      SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 1024, 2, 1>), dim3((unsigned)h->num_cus), dim3(1024),
-                  (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo,
-                  (const I *)(vlist + seg_max), 0, col_out, val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows,
-                  (const unsigned *)&st->n_seg[1], 0u);
-    }
-  }
+  // (512 threads, two workgroups per CU for segments of up to 4096 entries; 1024 threads for the longer ones)
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 512, 2, (VB == 8 ? 2 : 4)>), dim3(2 * (unsigned)h->num_cus), dim3(512),
+              (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo, (const I *)vlist, 0,
+              c.col_out, c.val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows, (const unsigned *)&st->n_seg[0], 0u);
+  if constexpr (VB != 8)
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_rows_quad<I, VB, 1024, 2, 1>), dim3((unsigned)h->num_cus), dim3(1024),
+                (const int2 *)vrec, (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo,
+                (const I *)(vlist + seg_max), 0, c.col_out, c.val_out, st, PERMUTE_ABLATE, fb_rows, &st->n_seg_fb_rows,
+                (const unsigned *)&st->n_seg[1], 0u);
   SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_permute_rows_radix<I, VB>), dim3(256), dim3(1024), (const int2 *)vrec,
-              (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo, (const unsigned *)fb_rows, col_out,
-              val_out, col_bits, st, (const unsigned *)&st->n_seg_fb_rows);
+              (const I *)c2, (const char *)v2, (const I *)nullptr, (const I *)vrpo, (const unsigned *)fb_rows, c.col_out,
+              c.val_out, c.col_bits, st, (const unsigned *)&st->n_seg_fb_rows);
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_PERMUTE_LONG, long_nnz * (int64_t)(2 * (sizeof(I) + VB)));
   PermState hs2;
@@ -2752,8 +2767,7 @@ int long_rows_path(sbx_handle_t h, const int2 *rec, const I *col_in, const char 
     fprintf(stderr, "long rows %u (%lld entries): segments %u + %u, clustered segments %u, rows left to the radix sort %u (%llu entries)\n",
             n_long, (long long)long_nnz, hs2.n_seg[0], hs2.n_seg[1], hs2.n_seg_fb_rows, hs2.n_long_fb, hs2.long_fb_nnz);
   if (hs2.n_long_fb)
-    SBX_TRY((long_rows_radix_path<I, VB>(h, rec, col_in, val_in, col_order, rpo, col_out, val_out, m, (const I *)fb_list,
-                                         hs2.n_long_fb, (int64_t)hs2.long_fb_nnz, st)));
+    SBX_TRY((long_rows_radix_path<I, VB>(c, (const I *)fb_list, hs2.n_long_fb, (int64_t)hs2.long_fb_nnz)));
   return SBX_OK;
 }
 
@@ -2816,10 +2830,10 @@ __global__ __launch_bounds__(256) void k_wide_scatter(const uint64_t *__restrict
 }
 
 template <typename I, int VB>
-int wide_rows_path(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *col_in, const char *val_in,
-                   const I *col_order, const I *rpo, I *col_out, char *val_out, int64_t nr, int64_t m, int64_t total,
-                   PermState *st) {
-  const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0), row_bits = sbx_bits_for(nr > 0 ? (uint64_t)(nr - 1) : 0);
+int wide_rows_path(const PermCall<I> &c) {
+  sbx_handle_t h = c.h;
+  const int64_t total = c.total;
+  const int col_bits = c.col_bits, row_bits = sbx_bits_for(c.nr > 0 ? (uint64_t)(c.nr - 1) : 0);
   if (col_bits + row_bits > 64)
     SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "permute: %d row bits + %d column bits do not fit a 64-bit sort key", row_bits, col_bits);
   uint64_t *ka = nullptr, *kb = nullptr;
@@ -2831,11 +2845,11 @@ int wide_rows_path(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *
     SBX_TRY(sbx_salloc(h, (size_t)total * VB, &pb));
   }
   const unsigned grid = sbx_grid_for(total, 256, 8192);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_wide_gather<I, VB>), dim3(grid), dim3(256), rec, col_in, val_in, col_order, rpo, nr,
-              total, col_bits, ka, pa, st);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_wide_gather<I, VB>), dim3(grid), dim3(256), c.rec, c.col_in, c.val_in, c.col_order,
+              c.rpo, c.nr, total, col_bits, ka, pa, c.st);
   SBX_LAUNCH_CHECK(h);
   PermState hs2;  // rows that are already ordered skip the sort
-  SBX_TRY(sbx_readback(h, &hs2, st, sizeof(PermState)));
+  SBX_TRY(sbx_readback(h, &hs2, c.st, sizeof(PermState)));
   int in_b = 0;
   if (hs2.long_unsorted && col_bits + row_bits > 0) {
     sbx_radix_pass passes[16];
@@ -2843,147 +2857,133 @@ int wide_rows_path(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *
     SBX_TRY(sbx_radix_sort(h, 8, VB, ka, kb, pa, pb, total, passes, np, &in_b));
   }
   SBX_KLAUNCH(h, SBX_K_PERMUTE_LONG, (k_wide_scatter<I, VB>), dim3(grid), dim3(256), (const uint64_t *)(in_b ? kb : ka),
-              (const char *)(in_b ? pb : pa), total, col_bits, col_out, val_out, st);
+              (const char *)(in_b ? pb : pa), total, col_bits, c.col_out, c.val_out, c.st);
   SBX_LAUNCH_CHECK(h);
   SBX_PROF_BYTES(h, SBX_K_PERMUTE_LONG, total * (int64_t)(2 * (sizeof(I) + VB)));
-  if (VB) SBX_TRY(launch_fix<I>(h, vt, rpo, (const I *)col_out, val_out, nr, st));
+  if (VB) SBX_TRY(launch_fix(c));
   return SBX_OK;
 }
 
-// Sort stage shared by permute and csr_sort_rows: rows of `rpo` (nr rows, already
-// on device) are produced from the source CSR through the row/col maps.
+// ---- the sort stage shared by the permute, csr_sort_rows and the segment sort ---------------------------------------
+// rows of up to PT_LMAX entries (short_nnz of them in all): the tile kernels, on the caller's stream
 template <typename I, int VB>
-int sort_stage(sbx_handle_t h, sbx_value_type vt, const int2 *rec, const I *col_in, const char *val_in,
-               const I *col_order, const I *rpo, I *col_out, char *val_out, int64_t nr, int64_t m,
-               int64_t total, const I *long_rows, const I *block_rows, int64_t block_stride,
-               const PermState &hs, PermState *st, const I *sp, const I *tile_first_ready = nullptr,
-               int64_t nnz_in = 0 /* entries of col_in / val_in */, const CdfMap *cdf = nullptr, bool cdf_on_side = false) {
-  if (cdf_on_side) {  // the map was built on side stream 1: everything from here on comes behind it
+int tile_rows_path(const PermCall<I> &c, int64_t short_nnz) {
+  sbx_handle_t h = c.h;
+  const int64_t tiles = (short_nnz + PT_W - 1) / PT_W;
+  const I *tile_first = c.tile_first;  // (from the classification pass, where it had the bounds to allocate it)
+  if (!tile_first) {
+    I *tf = nullptr;
+    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tf));
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_tile_first<I>, dim3((unsigned)(tiles / 256 + 1)), dim3(256), (const I *)c.sp, c.nr,
+                tiles, tf);
+    tile_first = tf;
+  }
+  unsigned *fb_tiles = nullptr;  // tiles whose rows cluster (listed by the tile kernel, sorted by its radix twin)
+  SBX_TRY(sbx_salloc(h, (size_t)tiles, &fb_tiles));
+  // persistent waves, 15 per CU (the LDS of a tile) times 12 (measured: 1 ... 2 per slot lose 10 % to imbalance — a
+  // tile is 30 ... 512 entries —, 8 ... 16 are level, one wave per tile is 7 % slower): each walks its tiles as a pipeline
+  const int64_t tile_grid = (int64_t)h->num_cus * 15 * TILE_GRID_FACTOR;
+  const dim3 grid((unsigned)(tiles < tile_grid ? tiles : tile_grid));
+  // the relabelling permutes whose arrays fit 32-bit byte offsets and whose ids fit the map's words: k_permute_tile2
+  constexpr uint64_t EB = sizeof(I) > (size_t)VB ? sizeof(I) : (size_t)VB;
+  const bool tile2 = c.cdf.table && c.col_order && !sbx_sw().permute_force_radix && !PERMUTE_ABLATING &&
+                     c.nnz_in < ((int64_t)1 << 28) && (uint64_t)c.nnz_in * EB <= PT2_MAX_BYTES &&
+                     (uint64_t)c.total * EB <= PT2_MAX_BYTES && (uint64_t)c.m * sizeof(I) <= PT2_MAX_BYTES;
+  if (tile2) {
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile2<I, VB>), grid, dim3(PT_THREADS), c.rec, c.col_in, c.val_in,
+                c.col_order, c.rpo, (const I *)c.sp, tile_first, c.col_out, c.val_out, c.nr, c.st, (int64_t)tiles,
+                (unsigned)((uint64_t)c.nnz_in * sizeof(I)), (unsigned)((uint64_t)c.nnz_in * VB),
+                (unsigned)((uint64_t)c.total * sizeof(I)), (unsigned)((uint64_t)c.total * VB),
+                (unsigned)((uint64_t)c.m * sizeof(I)), c.cdf);
+  } else {
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile<I, VB>), grid, dim3(PT_THREADS), c.rec, c.col_in, c.val_in,
+                c.col_order, c.rpo, (const I *)c.sp, tile_first, c.col_out, c.val_out, c.nr, c.st, c.col_bits,
+                (int)sbx_sw().permute_force_radix, fb_tiles, (int64_t)tiles);
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile_radix<I, VB>), dim3((unsigned)(tiles < 2048 ? tiles : 2048)),
+                dim3(PT_THREADS), c.rec, c.col_in, c.val_in, c.col_order, c.rpo, (const I *)c.sp, tile_first, c.col_out,
+                c.val_out, c.nr, c.st, c.col_bits, (const unsigned *)fb_tiles);
+  }
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_PERMUTE_TILE, short_nnz * (int64_t)(2 * (sizeof(I) + VB)));
+  if constexpr (TILE_STOP == 9) {  // diagnostic: print and clear the phase stamps
+    unsigned long long hs_[32];
+    SBX_HIP(h, hipStreamSynchronize(h->stream));
+    SBX_HIP(h, hipMemcpyFromSymbol(hs_, HIP_SYMBOL(g_tile_stamps), sizeof(hs_)));
+    if (hs_[31]) {
+      fprintf(stderr, "tile stamps: tiles %llu avg entries %.0f | cycles to end of phase:", hs_[31],
+              (double)hs_[30] / (double)hs_[31]);
+      for (int i = 0; i < 16; i++) fprintf(stderr, " [%d] %.0f", i, (double)hs_[i] / (double)hs_[31]);
+      fprintf(stderr, "\n");
+    }
+    memset(hs_, 0, sizeof(hs_));
+    SBX_HIP(h, hipMemcpyToSymbol(HIP_SYMBOL(g_tile_stamps), hs_, sizeof(hs_)));
+  }
+  return SBX_OK;
+}
+
+// Rows of c.rpo (already on the device) are produced from the source through the row records and the column map.
+template <typename I, int VB>
+int sort_stage(const PermCall<I> &c) {
+  sbx_handle_t h = c.h;
+  if (c.cdf_on_side) {  // the map was built on side stream 1: everything from here on comes behind it
     SBX_HIP(h, hipStreamWaitEvent(h->stream, h->aux_event[2], 0));
     h->aux_dirty = false;
   }
   if constexpr (sizeof(I) == 8)
-    if (m > KEY32_MAX_COLS)
-      return wide_rows_path<I, VB>(h, vt, rec, col_in, val_in, col_order, rpo, col_out, val_out, nr, m, total, st);
-  const unsigned n_long = hs.n_long;
-  const unsigned *n_block = hs.n_block;
-  const int64_t long_nnz = (int64_t)hs.long_nnz, block_nnz = (int64_t)hs.block_nnz;
+    if (c.m > KEY32_MAX_COLS) return wide_rows_path<I, VB>(c);
   // The three paths write disjoint rows of the output and only read the inputs: with more than one of them
   // present they run on streams of their own (tile kernel on the caller's stream), so the block-row kernels'
   // tails and the long-row path's short, latency-bound launches hide behind the tile kernel.  While the
   // profiler is on they run back to back, so that a kernel's event time is its own.
+  const bool has_long = c.hs.n_long != 0;
   bool has_block = false;
-  for (int c = 0; c < BR_CLASSES; c++) has_block |= n_block[c] != 0;
-  const bool fork = !h->prof_on && sbx_sw().permute_overlap && total > 0 && (has_block || n_long);
-  (void)total;
+  for (int cls = 0; cls < BR_CLASSES; cls++) has_block |= c.hs.n_block[cls] != 0;
+  const bool fork = !h->prof_on && sbx_sw().permute_overlap && c.total > 0 && (has_block || has_long);
   hipStream_t main_stream = h->stream;
   if (fork) {
     SBX_TRY(sbx_aux_streams(h));
     SBX_HIP(h, hipEventRecord(h->aux_event[0], main_stream));
     h->aux_dirty = true;
     if (has_block) SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[0], h->aux_event[0], 0));
-    if (n_long) SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[0], 0));
+    if (has_long) SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[0], 0));
   }
-  const int64_t short_nnz = total - long_nnz - block_nnz;  // entries of the rows the tile kernel sorts
-  if (short_nnz > 0) {
-    const int64_t tiles = (short_nnz + PT_W - 1) / PT_W;
-    const I *tile_first = tile_first_ready;  // (from the classification pass, where it had the bounds to allocate it)
-    if (!tile_first) {
-      I *tf = nullptr;
-      SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tf));
-      SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_tile_first<I>, dim3((unsigned)(tiles / 256 + 1)), dim3(256), sp, nr, tiles, tf);
-      tile_first = tf;
-    }
-    unsigned *fb_tiles = nullptr;  // tiles whose rows cluster (listed by the tile kernel, sorted by its radix twin)
-    SBX_TRY(sbx_salloc(h, (size_t)tiles, &fb_tiles));
-    const int col_bits = sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0);
-    // persistent waves, 15 per CU (the LDS of a tile) times 12 (measured: 1 ... 2 per slot lose 10 % to imbalance — a
-    // tile is 30 ... 512 entries —, 8 ... 16 are level, one wave per tile is 7 % slower): each walks its tiles as a pipeline
-    const int64_t tile_grid = (int64_t)h->num_cus * 15 * TILE_GRID_FACTOR;
-    // the relabelling permutes whose arrays fit 32-bit byte offsets and whose ids fit the map's words: k_permute_tile2
-    constexpr uint64_t EB = sizeof(I) > (size_t)VB ? sizeof(I) : (size_t)VB;
-    const bool tile2 = cdf && cdf->table && col_order && !sbx_sw().permute_force_radix && !PERMUTE_ABLATING && nnz_in < ((int64_t)1 << 28) &&
-                       (uint64_t)nnz_in * EB <= PT2_MAX_BYTES && (uint64_t)total * EB <= PT2_MAX_BYTES &&
-                       (uint64_t)m * sizeof(I) <= PT2_MAX_BYTES;
-    if (tile2) {
-      SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile2<I, VB>), dim3((unsigned)(tiles < tile_grid ? tiles : tile_grid)),
-                  dim3(PT_THREADS), rec, col_in, val_in, col_order, rpo, sp, (const I *)tile_first, col_out, val_out, nr,
-                  st, (int64_t)tiles, (unsigned)((uint64_t)nnz_in * sizeof(I)), (unsigned)((uint64_t)nnz_in * VB),
-                  (unsigned)((uint64_t)total * sizeof(I)), (unsigned)((uint64_t)total * VB),
-                  (unsigned)((uint64_t)m * sizeof(I)), *cdf);
-    } else {
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile<I, VB>), dim3((unsigned)(tiles < tile_grid ? tiles : tile_grid)),
-                dim3(PT_THREADS), rec, col_in, val_in, col_order, rpo, sp, (const I *)tile_first, col_out, val_out, nr,
-                st, col_bits, (int)sbx_sw().permute_force_radix, fb_tiles, (int64_t)tiles);
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_tile_radix<I, VB>), dim3((unsigned)(tiles < 2048 ? tiles : 2048)),
-                dim3(PT_THREADS), rec, col_in, val_in, col_order, rpo, sp, (const I *)tile_first, col_out, val_out, nr,
-                st, col_bits, (const unsigned *)fb_tiles);
-    }
-    SBX_LAUNCH_CHECK(h);
-    SBX_PROF_BYTES(h, SBX_K_PERMUTE_TILE, short_nnz * (int64_t)(2 * (sizeof(I) + VB)));
-    if constexpr (TILE_STOP == 9) {  // diagnostic: print and clear the phase stamps
-      unsigned long long hs_[32];
-      SBX_HIP(h, hipStreamSynchronize(h->stream));
-      SBX_HIP(h, hipMemcpyFromSymbol(hs_, HIP_SYMBOL(g_tile_stamps), sizeof(hs_)));
-      if (hs_[31]) {
-        fprintf(stderr, "tile stamps: tiles %llu avg entries %.0f | cycles to end of phase:", hs_[31],
-                (double)hs_[30] / (double)hs_[31]);
-        for (int i = 0; i < 16; i++) fprintf(stderr, " [%d] %.0f", i, (double)hs_[i] / (double)hs_[31]);
-        fprintf(stderr, "\n");
-      }
-      memset(hs_, 0, sizeof(hs_));
-      SBX_HIP(h, hipMemcpyToSymbol(HIP_SYMBOL(g_tile_stamps), hs_, sizeof(hs_)));
-    }
-  }
+  const int64_t short_nnz = c.total - (int64_t)c.hs.long_nnz - (int64_t)c.hs.block_nnz;
+  if (short_nnz > 0) SBX_TRY((tile_rows_path<I, VB>(c, short_nnz)));
   if (has_block) {
-    if (fork) h->stream = h->aux_stream[0];
-    const int rc = block_rows_path<I, VB>(h, rec, col_in, val_in, col_order, rpo, col_out, val_out, m, block_rows, n_block,
-                                       block_stride, block_nnz, st, fork);
-    if (fork) {
-      if (rc == SBX_OK && hipEventRecord(h->aux_event[1], h->stream) != hipSuccess) { h->stream = main_stream; SBX_FAIL(h, SBX_ERR_HIP, "hipEventRecord failed"); }
-      h->stream = main_stream;
-    }
-    SBX_TRY(rc);
+    sbx_stream_scope on_side(h, fork ? h->aux_stream[0] : main_stream);
+    SBX_TRY((block_rows_path<I, VB>(c, fork)));
+    if (fork) SBX_HIP(h, hipEventRecord(h->aux_event[1], h->stream));
   }
-  if (n_long) {
-    if (fork) h->stream = h->aux_stream[1];
-    const int rc = long_rows_path<I, VB>(h, rec, col_in, val_in, col_order, rpo, col_out, val_out, m, long_rows, n_long,
-                                         long_nnz, st);
-    if (fork) {
-      if (rc == SBX_OK && hipEventRecord(h->aux_event[2], h->stream) != hipSuccess) { h->stream = main_stream; SBX_FAIL(h, SBX_ERR_HIP, "hipEventRecord failed"); }
-      h->stream = main_stream;
-    }
-    SBX_TRY(rc);
+  if (has_long) {
+    sbx_stream_scope on_side(h, fork ? h->aux_stream[1] : main_stream);
+    SBX_TRY((long_rows_path<I, VB>(c)));
+    if (fork) SBX_HIP(h, hipEventRecord(h->aux_event[2], h->stream));
   }
   if (fork) {  // join
     if (has_block) SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[1], 0));
-    if (n_long) SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[2], 0));
+    if (has_long) SBX_HIP(h, hipStreamWaitEvent(main_stream, h->aux_event[2], 0));
     h->aux_dirty = false;
   }
-  if (VB) SBX_TRY(launch_fix<I>(h, vt, rpo, col_out, val_out, nr, st));
+  if (VB) SBX_TRY(launch_fix(c));
   return SBX_OK;
 }
 
-// The call's state, the classification's look-back words and the row records in ONE allocation, zeroed by ONE fill
-// (three fills cost three launches of ~4.5 us in front of the first kernel).  status: for classify_and_scan.
+// ---- the preparation --------------------------------------------------------------------------------------------------
 static int64_t cs_tiles(int64_t nr) { return (nr + CS_TILE - 1) / CS_TILE > 0 ? (nr + CS_TILE - 1) / CS_TILE : 1; }
 // The call's state, the classification's tile sums and the row records in ONE allocation, zeroed by ONE fill (three
 // fills cost three launches of ~4.5 us in front of the first kernel; the records of rows a malformed row order never
 // names must read as empty).  status: for classify_and_scan.
-static int perm_prep_alloc(sbx_handle_t h, int64_t nr, PermState **st, unsigned long long **status, int2 **rec) {
-  const size_t status_bytes = sizeof(unsigned long long) * (size_t)(2 * cs_tiles(nr) + 2);
-  const size_t bytes = sizeof(PermAll) + status_bytes + sizeof(int2) * (size_t)nr;
+template <typename I>
+int perm_prep_alloc(PermCall<I> &c, unsigned long long **status, int2 **rec) {
+  const size_t status_bytes = sizeof(unsigned long long) * (size_t)(2 * cs_tiles(c.nr) + 2);
+  const size_t bytes = sizeof(PermAll) + status_bytes + sizeof(int2) * (size_t)c.nr;
   char *base = nullptr;
-  SBX_TRY(sbx_salloc(h, bytes + 128, &base));
+  SBX_TRY(sbx_salloc(c.h, bytes + 128, &base));
   base = (char *)(((uintptr_t)base + 127) & ~(uintptr_t)127);  // (PermAll keeps its counters on lines of their own)
-  *st = &((PermAll *)base)->st;
+  c.st = &((PermAll *)base)->st;
   *status = (unsigned long long *)(base + sizeof(PermAll));
-  *rec = (int2 *)(base + sizeof(PermAll) + status_bytes);
-  SBX_HIP(h, hipMemsetAsync(base, 0, bytes, h->stream));
-  return SBX_OK;
-}
-static int perm_state_zero(sbx_handle_t h, PermState *st) {
-  SBX_HIP(h, hipMemsetAsync((PermAll *)st, 0, sizeof(PermAll), h->stream));
+  c.rec = *rec = (int2 *)(base + sizeof(PermAll) + status_bytes);
+  SBX_HIP(c.h, hipMemsetAsync(base, 0, bytes, c.h->stream));
   return SBX_OK;
 }
 // the state of the call on the host, the classification's counters folded in
@@ -2998,30 +2998,153 @@ static int perm_fetch(sbx_handle_t h, PermState *hs, const PermState *st) {
   return SBX_OK;
 }
 
-// rpo (may be nullptr: lengths already scanned), sp and the class lists (block_rows nullptr: none) in one launch;
-// st must have been zeroed by the caller
+// the lists of the rows that do not fit a tile: room for cap_long rows per class
 template <typename I>
-int classify_and_scan(sbx_handle_t h, const int2 *rec, I *rpo, I *sp, int64_t nr, I *long_rows, I *block_rows,
-                      int64_t block_stride, int block_cap, PermState *st, unsigned long long *status = nullptr,
-                      I **tile_first_out = nullptr, int64_t entries_upper = 0) {
-  const int64_t tiles = cs_tiles(nr);
-  if (!status) SBX_TRY(sbx_salloc(h, (size_t)(2 * tiles + 2), &status));  // (else: the words from perm_prep_alloc)
-  I *tile_first = nullptr;
-  if (tile_first_out) {  // the tile kernel's row ranges come out of the same pass (entries_upper >= the short rows' entries)
-    const int64_t slots = entries_upper / PT_W + 3;
-    SBX_TRY(sbx_salloc(h, (size_t)slots, &tile_first));
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_fill_index<I>, dim3(sbx_grid_for(slots, 256, 1024)), dim3(256), tile_first, slots,
-                (I)nr);
-    *tile_first_out = tile_first;
-  }
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_reduce, dim3((unsigned)tiles), dim3(256), rec, nr, status);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_prefix<I>, dim3(1), dim3(1024), status, tiles, rpo, sp, nr, st);
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_scan<I>, dim3((unsigned)tiles), dim3(256), rec, rpo, sp, nr, long_rows,
-              block_rows, block_stride, block_cap, st, (const unsigned long long *)status,
-              (int)(((uintptr_t)rpo & 15) == 0), tile_first);
+int alloc_class_lists(PermCall<I> &c, int64_t cap_long) {
+  SBX_TRY(sbx_salloc(c.h, (size_t)cap_long, &c.long_rows));
+  SBX_TRY(sbx_salloc(c.h, (size_t)cap_long * BR_CLASSES, &c.block_rows));
+  c.block_stride = cap_long;
+  return SBX_OK;
+}
+
+// the tile kernels' row ranges come out of the classification pass when it is given the slots: one per PT_W of
+// entries_upper (>= the short rows' entries), preset to "no row"
+template <typename I>
+int alloc_tile_first(PermCall<I> &c, int64_t entries_upper) {
+  const int64_t slots = entries_upper / PT_W + 3;
+  SBX_TRY(sbx_salloc(c.h, (size_t)slots, &c.tile_first));
+  SBX_KLAUNCH(c.h, SBX_K_PERMUTE_PREP, k_fill_index<I>, dim3(sbx_grid_for(slots, 256, 1024)), dim3(256), c.tile_first, slots,
+              (I)c.nr);
+  return SBX_OK;
+}
+
+// rpo_out (may be nullptr: lengths already scanned), sp and the class lists (block_rows nullptr: none) in one pass over
+// the records; c.st must have been zeroed.  status: nullptr, or the words from perm_prep_alloc
+template <typename I>
+int classify_and_scan(PermCall<I> &c, I *rpo_out, unsigned long long *status) {
+  sbx_handle_t h = c.h;
+  const int64_t tiles = cs_tiles(c.nr);
+  const int block_cap = c.vb == 8 ? BlockRowCap<8>::value : BlockRowCap<4>::value;
+  if (!status) SBX_TRY(sbx_salloc(h, (size_t)(2 * tiles + 2), &status));
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_reduce, dim3((unsigned)tiles), dim3(256), c.rec, c.nr, status);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_prefix<I>, dim3(1), dim3(1024), status, tiles, rpo_out, c.sp, c.nr, c.st);
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_classify_scan<I>, dim3((unsigned)tiles), dim3(256), c.rec, rpo_out, c.sp, c.nr,
+              c.long_rows, c.block_rows, c.block_stride, block_cap, c.st, (const unsigned long long *)status,
+              (int)(((uintptr_t)rpo_out & 15) == 0), c.tile_first);
   SBX_LAUNCH_CHECK(h);
   return SBX_OK;
 }
+
+// the key-distribution map of the relabelled columns (k_cdf_sample): needs nothing but the caller's arrays, so it is
+// built beside the preparation — on side stream 1, behind an event that orders it after the caller's earlier work
+// (c.cdf.table stays nullptr where no map applies)
+template <typename I>
+int cdf_map_beside(PermCall<I> &c) {
+  sbx_handle_t h = c.h;
+  if (!c.col_order || c.nnz_in <= 0 || sbx_sw().permute_no_tile2) return SBX_OK;
+  const bool side = !h->prof_on && sbx_sw().permute_overlap && sbx_aux_streams(h) == SBX_OK;
+  if (side) {
+    SBX_HIP(h, hipEventRecord(h->aux_event[0], h->stream));
+    SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[0], 0));
+    h->aux_dirty = true;
+  }
+  sbx_stream_scope on_side(h, side ? h->aux_stream[1] : h->stream);
+  if (c.col_bits <= CDF_MAX_COL_BITS) {
+    unsigned *hist = nullptr;
+    uint2 *table = nullptr;
+    SBX_TRY(sbx_salloc(h, (size_t)CDF_K, &hist));
+    SBX_TRY(sbx_salloc(h, (size_t)CDF_K, &table));
+    SBX_HIP(h, hipMemsetAsync(hist, 0, sizeof(unsigned) * CDF_K, h->stream));
+    const int shift = c.col_bits > CDF_LOG_K ? c.col_bits - CDF_LOG_K : 0;
+    const int64_t want = (c.nnz_in + 256 * CDF_SAMPLE_ITEMS - 1) / (256 * CDF_SAMPLE_ITEMS);
+    const unsigned blocks = (unsigned)(want < CDF_SAMPLE_BLOCKS ? want : CDF_SAMPLE_BLOCKS);
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_cdf_sample<I>, dim3(blocks), dim3(256), c.col_in, c.col_order, c.nnz_in, c.m, shift,
+                hist);
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_cdf_table, dim3(1), dim3(CDF_K), (const unsigned *)hist, table, shift == 0 ? 1 : 0);
+    SBX_LAUNCH_CHECK(h);
+    c.cdf.table = table, c.cdf.shift = shift, c.cdf.fsh = shift ? 32 - shift : 0;
+  }
+  if (side) SBX_HIP(h, hipEventRecord(h->aux_event[2], h->stream));
+  c.cdf_on_side = side;
+  return SBX_OK;
+}
+
+// The one preparation.  The entry has filled the context's first block; this fills the rest: the records of the new rows
+// [row_begin, row_begin + c.nr) of the n-row source `rp` under row_order (nullptr: identity), sp, the class lists
+// (cap_long rows each; 0: none), rpo_out (nullptr: c.rpo holds the scanned lengths already), the state on the host.  A
+// permute that relabels gets its map, forked behind the fill of the state and in front of the records, and tile_first.
+template <typename I>
+int perm_prepare(PermCall<I> &c, const I *rp, const I *row_order, int64_t n, int64_t row_begin, I *rpo_out,
+                 int64_t cap_long) {
+  sbx_handle_t h = c.h;
+  c.col_bits = sbx_bits_for(c.m > 0 ? (uint64_t)(c.m - 1) : 0);
+  unsigned long long *status = nullptr;
+  int2 *rec = nullptr;
+  SBX_TRY(perm_prep_alloc(c, &status, &rec));
+  SBX_TRY(cdf_map_beside(c));
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_rowwise_prep<I>, dim3(sbx_grid_for((n + 3) / 4, 256, 8192)), dim3(256), rp,
+              row_order, n, row_begin, c.nr, rec);
+  SBX_TRY(sbx_salloc(h, (size_t)c.nr + 1, &c.sp));
+  if (cap_long) SBX_TRY(alloc_class_lists(c, cap_long));
+  if (c.col_order) SBX_TRY(alloc_tile_first(c, c.nnz_in));
+  SBX_TRY(classify_and_scan(c, rpo_out, status));
+  // (the full row-wise permute keeps every nonzero and needs no class counts: no read-back)
+  if (cap_long || c.nr != n) SBX_TRY(perm_fetch(h, &c.hs, c.st));
+  else c.hs.total = (unsigned long long)c.nnz_in;
+  return SBX_OK;
+}
+
+// ---- the steps that are the full permute's own --------------------------------------------------------------------
+// a shard learns its size from the classification (the full permute keeps every nonzero); the caller's slab must hold it
+template <typename I>
+int check_capacity(PermCall<I> &c, int64_t out_capacity, int64_t *shard_nnz_host) {
+  c.total = (int64_t)c.hs.total;
+  if (shard_nnz_host) *shard_nnz_host = c.total;
+  if (c.total > out_capacity)
+    SBX_FAIL(c.h, SBX_ERR_BAD_ARG, "sbx_permute_csr_rows: shard needs %lld entries, capacity %lld", (long long)c.total,
+             (long long)out_capacity);
+  return SBX_OK;
+}
+
+// row-wise: a segmented copy; sorted input rows (every CSR that went through a constructor) end here (*done).  If some
+// input row is out of order the call is redone by the sorting pipeline, which needs the class lists (cap_long rows
+// each; row_ptr_out and sp are already final): classified again here
+template <typename I>
+int rowwise_copy(PermCall<I> &c, int64_t cap_long, bool *done) {
+  sbx_handle_t h = c.h;
+  const unsigned tiles = (unsigned)((c.total + PC_TILE - 1) / PC_TILE);
+  I *tile_row = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_row));
+  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_tile_rows<I>, dim3(tiles / 256 + 1), dim3(256), c.rpo, c.nr, c.total, PC_TILE,
+              (int64_t)tiles, tile_row);
+  SBX_TRY(with_value_bytes(c.vb, [&](auto w) -> int {
+    SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_copy<I, decltype(w)::value>), dim3(tiles), dim3(PC_THREADS), c.rec,
+                (const I *)tile_row, c.col_in, c.val_in, c.rpo, c.col_out, c.val_out, c.nr, c.total, c.st);
+    return SBX_OK;
+  }));
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_PERMUTE_TILE, c.total * (int64_t)(2 * (sizeof(I) + c.vb)));
+  PermState hc;
+  SBX_TRY(sbx_readback(h, &hc, c.st, sizeof(PermState)));
+  *done = !hc.any_unsorted;
+  if (*done) return SBX_OK;
+  SBX_TRY(alloc_class_lists(c, cap_long));
+  SBX_HIP(h, hipMemsetAsync((PermAll *)c.st, 0, sizeof(PermAll), h->stream));
+  SBX_TRY(classify_and_scan(c, (I *)nullptr, nullptr));
+  SBX_TRY(perm_fetch(h, &c.hs, c.st));
+  c.hs.total = (unsigned long long)c.total;
+  return SBX_OK;
+}
+
+// the arguments of sbx_permute_csr_rows, as the entry point got them
+struct PermuteArgs {
+  sbx_value_type vt;
+  int64_t n, m, nnz;
+  const void *row_ptr, *col, *val, *row_order, *col_order;
+  int64_t row_begin, row_end;
+  void *row_ptr_out, *col_out, *val_out;
+  int64_t out_capacity, *shard_nnz_host;
+};
 
 }  // namespace
 
@@ -3042,6 +3165,17 @@ extern "C" int sbx_inverse_permutation(sbx_handle_t h, sbx_index_type it, int64_
   return SBX_OK;
 }
 
+template <typename I>
+static int permute_array_typed(sbx_handle_t h, int vb, int64_t n, const void *order, const void *vals, void *out) {
+  return with_value_bytes(vb, [&](auto w) -> int {
+    if constexpr (decltype(w)::value != 0)  // (the entry point has refused other widths)
+      SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, (k_permute_array<I, decltype(w)::value>), dim3(sbx_grid_for(n, 256, 8192)),
+                  dim3(256), (const I *)order, (const char *)vals, (char *)out, n);
+    SBX_LAUNCH_CHECK(h);
+    return SBX_OK;
+  });
+}
+
 extern "C" int sbx_permute_array(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, const void *order,
                                  const void *vals, void *out) {
   if (!h) return SBX_ERR_BAD_ARG;
@@ -3051,141 +3185,40 @@ extern "C" int sbx_permute_array(sbx_handle_t h, sbx_index_type it, sbx_value_ty
   SBX_REQUIRE(h, vb == 4 || vb == 8, "value type must be 4 or 8 bytes");
   SBX_TRY(sbx_arena_begin(h));
   if (n == 0) return SBX_OK;
-  const unsigned grid = sbx_grid_for(n, 256, 8192);
-  if (it == SBX_I64) {  // (native: no narrowed copy of the order)
-    if (vb == 4)
-      SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, (k_permute_array<int64_t, 4>), dim3(grid), dim3(256), (const int64_t *)order,
-                  (const char *)vals, (char *)out, n);
-    else
-      SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, (k_permute_array<int64_t, 8>), dim3(grid), dim3(256), (const int64_t *)order,
-                  (const char *)vals, (char *)out, n);
-  } else if (vb == 4)
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, (k_permute_array<int32_t, 4>), dim3(grid), dim3(256), (const int32_t *)order,
-                       (const char *)vals, (char *)out, n);
-  else
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, (k_permute_array<int32_t, 8>), dim3(grid), dim3(256), (const int32_t *)order,
-                       (const char *)vals, (char *)out, n);
-  SBX_LAUNCH_CHECK(h);
-  return SBX_OK;
+  if (it == SBX_I64) return permute_array_typed<int64_t>(h, vb, n, order, vals, out);  // (native: no narrowed copy of the order)
+  return permute_array_typed<int32_t>(h, vb, n, order, vals, out);
 }
 
 // One shard of the permute for either index width.  The records (length, source offset) stay 32-bit — nnz < 2^31, checked
 // by the caller — while row_ptr, the orders and the columns are read and written as they are: no narrowed copies.
 template <typename I>
-static int permute_csr_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, int64_t nnz, const void *row_ptr,
-                                  const void *col, const void *val, const void *row_order, const void *col_order,
-                                  int64_t row_begin, int64_t row_end, void *row_ptr_out, void *col_out, void *val_out,
-                                  int64_t out_capacity, int64_t *shard_nnz_host) {
-  const int vb = (val && val_out) ? sbx_value_bytes(vt) : 0;
+static int permute_csr_rows_typed(sbx_handle_t h, const PermuteArgs &a) {
+  const int vb = (a.val && a.val_out) ? sbx_value_bytes(a.vt) : 0;
   SBX_REQUIRE(h, vb >= 0, "unknown value type");
   SBX_TRY(sbx_arena_begin(h));
-  sbx_aux_scope aux_scope(h);  // (the map's fork below and the sort stage's: no way out of this function leaves one open)
-  const int64_t nr = row_end - row_begin;
-  I *rpo = (I *)row_ptr_out;
-  if (shard_nnz_host) *shard_nnz_host = 0;
+  sbx_aux_scope aux_scope(h);  // (the map's fork and the sort stage's: no way out of this function leaves one open)
+  const int64_t nr = a.row_end - a.row_begin;
+  I *rpo = (I *)a.row_ptr_out;
+  if (a.shard_nnz_host) *a.shard_nnz_host = 0;
   if (nr == 0) {
     if constexpr (sizeof(I) == 8) return sbx_fill_i64(h, (int64_t *)rpo, 0, 1);
     else return sbx_fill_i32(h, (int32_t *)rpo, 0, 1);
   }
-
-  // (row length, source offset) per new row, written from the old-row side; lengths -> scan -> row_ptr_out
-  PermState *st = nullptr;
-  int2 *rec = nullptr;
-  unsigned long long *status = nullptr;
-  SBX_TRY(perm_prep_alloc(h, nr, &st, &status, &rec));
-  // the key-distribution map of the relabelled columns (k_cdf_sample): needs nothing but the caller's arrays, so it is
-  // built beside the preparation — on side stream 1, behind an event that orders it after the caller's earlier work
-  CdfMap cdf;
-  cdf.table = nullptr, cdf.shift = 0, cdf.fsh = 0;
-  bool cdf_on_side = false;
-  if (col_order && nnz > 0 && !sbx_sw().permute_no_tile2) {
-    if (!h->prof_on && sbx_sw().permute_overlap && sbx_aux_streams(h) == SBX_OK) {
-      hipStream_t main_stream = h->stream;
-      SBX_HIP(h, hipEventRecord(h->aux_event[0], main_stream));
-      SBX_HIP(h, hipStreamWaitEvent(h->aux_stream[1], h->aux_event[0], 0));
-      h->aux_dirty = true;
-      h->stream = h->aux_stream[1];
-      const int rc_cdf = build_cdf_map<I>(h, (const I *)col, (const I *)col_order, nnz, m, &cdf);
-      const hipError_t e_cdf = rc_cdf == SBX_OK ? hipEventRecord(h->aux_event[2], h->stream) : hipSuccess;
-      h->stream = main_stream;
-      SBX_TRY(rc_cdf);
-      if (e_cdf != hipSuccess) SBX_FAIL(h, SBX_ERR_HIP, "hipEventRecord failed");
-      cdf_on_side = true;
-    } else {
-      SBX_TRY(build_cdf_map<I>(h, (const I *)col, (const I *)col_order, nnz, m, &cdf));
-    }
+  PermCall<I> c = {};
+  c.h = h, c.vt = a.vt, c.vb = vb, c.nr = nr, c.m = a.m, c.nnz_in = a.nnz;
+  c.col_in = (const I *)a.col, c.val_in = (const char *)a.val, c.col_order = (const I *)a.col_order;
+  c.rpo = rpo, c.col_out = (I *)a.col_out, c.val_out = (char *)a.val_out;
+  // the sorting pipeline needs the rows that do not fit a tile listed by class; lengths -> row_ptr_out
+  const int64_t cap_long = a.nnz / PT_LMAX + 1 > nr ? nr : a.nnz / PT_LMAX + 1;
+  SBX_TRY(perm_prepare(c, (const I *)a.row_ptr, (const I *)a.row_order, a.n, a.row_begin, rpo, c.col_order ? cap_long : 0));
+  SBX_TRY(check_capacity(c, a.out_capacity, a.shard_nnz_host));
+  if (c.total == 0) return SBX_OK;
+  if (!c.col_order) {
+    bool done = false;
+    SBX_TRY(rowwise_copy(c, cap_long, &done));
+    if (done) return SBX_OK;
   }
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_rowwise_prep<I>, dim3(sbx_grid_for((n + 3) / 4, 256, 8192)), dim3(256),
-              (const I *)row_ptr, (const I *)row_order, n, row_begin, nr, rec);
-  I *long_rows = nullptr, *block_rows = nullptr, *sp = nullptr;
-  const int block_cap = vb == 8 ? BlockRowCap<8>::value : BlockRowCap<4>::value;
-  int64_t block_stride = 0;
-  SBX_TRY(sbx_salloc(h, (size_t)nr + 1, &sp));
-  if (col_order) {  // the sorting pipeline needs the rows that do not fit a tile listed by class
-    int64_t cap_long = nnz / PT_LMAX + 1;
-    if (cap_long > nr) cap_long = nr;
-    SBX_TRY(sbx_salloc(h, (size_t)cap_long, &long_rows));
-    SBX_TRY(sbx_salloc(h, (size_t)cap_long * BR_CLASSES, &block_rows));
-    block_stride = cap_long;
-  }
-  // lengths -> row_ptr_out, the short rows' prefix sums and the class lists: one launch
-  I *tile_first = nullptr;
-  SBX_TRY(classify_and_scan<I>(h, (const int2 *)rec, rpo, sp, nr, long_rows, block_rows, block_stride, block_cap, st,
-                               status, col_order ? &tile_first : nullptr, nnz));
-  int64_t total = nnz;  // the full permute keeps every nonzero; a shard has to ask
-  PermState hs;
-  memset(&hs, 0, sizeof(hs));
-  if (nr != n || col_order) {
-    SBX_TRY(perm_fetch(h, &hs, st));
-    total = (int64_t)hs.total;
-  }
-  if (shard_nnz_host) *shard_nnz_host = total;
-  if (total > out_capacity)
-    SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbx_permute_csr_rows: shard needs %lld entries, capacity %lld", (long long)total,
-             (long long)out_capacity);
-  if (total == 0) return SBX_OK;
-  if (!col_order) {
-    // row-wise: a segmented copy; sorted input rows (every CSR that went through a constructor) end here
-    const unsigned tiles = (unsigned)((total + PC_TILE - 1) / PC_TILE);
-    I *tile_row = nullptr;
-    SBX_TRY(sbx_salloc(h, (size_t)tiles + 1, &tile_row));
-    SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_tile_rows<I>, dim3(tiles / 256 + 1), dim3(256), (const I *)rpo, nr, total,
-                PC_TILE, (int64_t)tiles, tile_row);
-#define COPY(VBX)                                                                                              \
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_TILE, (k_permute_copy<I, VBX>), dim3(tiles), dim3(PC_THREADS), (const int2 *)rec, \
-              (const I *)tile_row, (const I *)col, (const char *)val, (const I *)rpo, (I *)col_out, (char *)val_out, \
-              nr, total, st)
-    if (vb == 0) COPY(0);
-    else if (vb == 4) COPY(4);
-    else COPY(8);
-#undef COPY
-    SBX_LAUNCH_CHECK(h);
-    SBX_PROF_BYTES(h, SBX_K_PERMUTE_TILE, total * (int64_t)(2 * (sizeof(I) + vb)));
-    PermState hc;
-    SBX_TRY(sbx_readback(h, &hc, st, sizeof(PermState)));
-    if (!hc.any_unsorted) return SBX_OK;
-    // some input row is out of order: redo with the sorting pipeline (row_ptr_out is already final)
-    int64_t cap_long = nnz / PT_LMAX + 1;
-    if (cap_long > nr) cap_long = nr;
-    SBX_TRY(sbx_salloc(h, (size_t)cap_long, &long_rows));
-    SBX_TRY(sbx_salloc(h, (size_t)cap_long * BR_CLASSES, &block_rows));
-    block_stride = cap_long;
-    SBX_TRY(perm_state_zero(h, st));
-    SBX_TRY(classify_and_scan<I>(h, (const int2 *)rec, (I *)nullptr, sp, nr, long_rows, block_rows, block_stride,
-                                 block_cap, st));
-    SBX_TRY(perm_fetch(h, &hs, st));
-    hs.total = (unsigned long long)total;
-  }
-  int rc;
-#define STAGE(VBX)                                                                                                  \
-  rc = sort_stage<I, VBX>(h, vt, (const int2 *)rec, (const I *)col, (const char *)val, (const I *)col_order, rpo,      \
-                       (I *)col_out, (char *)val_out, nr, m, total, long_rows, block_rows, block_stride, hs, st, sp, \
-                       (const I *)tile_first, nnz, &cdf, cdf_on_side)
-  if (vb == 0) STAGE(0);
-  else if (vb == 4) STAGE(4);
-  else STAGE(8);
-#undef STAGE
-  return rc;
+  return with_value_bytes(vb, [&](auto w) -> int { return sort_stage<I, decltype(w)::value>(c); });
 }
 
 extern "C" int sbx_permute_csr_rows(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m,
@@ -3201,11 +3234,9 @@ extern "C" int sbx_permute_csr_rows(sbx_handle_t h, sbx_index_type it, sbx_value
   SBX_REQUIRE(h, 0 <= row_begin && row_begin <= row_end && row_end <= n, "bad row range");
   SBX_REQUIRE(h, nnz == 0 || (col && col_out), "col/col_out required");
   SBX_REQUIRE(h, nnz < ((int64_t)1 << 31) && n < ((int64_t)1 << 31) - 1, "dimension exceeds int32");
-  if (it == SBX_I64)
-    return permute_csr_rows_typed<int64_t>(h, vt, n, m, nnz, row_ptr, col, val, row_order, col_order, row_begin, row_end,
-                                           row_ptr_out, col_out, val_out, out_capacity, shard_nnz_host);
-  return permute_csr_rows_typed<int32_t>(h, vt, n, m, nnz, row_ptr, col, val, row_order, col_order, row_begin, row_end,
-                                         row_ptr_out, col_out, val_out, out_capacity, shard_nnz_host);
+  const PermuteArgs a = {vt, n, m, nnz, row_ptr, col, val, row_order, col_order, row_begin, row_end, row_ptr_out, col_out,
+                         val_out, out_capacity, shard_nnz_host};
+  return it == SBX_I64 ? permute_csr_rows_typed<int64_t>(h, a) : permute_csr_rows_typed<int32_t>(h, a);
 }
 
 extern "C" int sbx_permute_csr(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m, int64_t nnz,
@@ -3215,7 +3246,14 @@ extern "C" int sbx_permute_csr(sbx_handle_t h, sbx_index_type it, sbx_value_type
                               col_out, val_out, nnz, nullptr);
 }
 
-// A4: the CSR constructor's "if any row is unsorted, sort every row" in place.
+// The sort stage with identity maps: every row of `rp` (n rows over m columns, nnz entries) sorted out of place.
+template <typename I>
+static int sort_rows_out_of_place(PermCall<I> &c, const I *rp, int64_t n, int64_t nnz) {
+  c.nr = n, c.rpo = rp, c.col_order = nullptr, c.total = nnz, c.nnz_in = nnz;
+  SBX_TRY(perm_prepare(c, rp, (const I *)nullptr, n, (int64_t)0, (I *)nullptr, n));
+  return with_value_bytes(c.vb, [&](auto w) -> int { return sort_stage<I, decltype(w)::value>(c); });
+}
+
 // Stable sort of every segment of (key, value) pairs by its 32-bit key, out of place: the sort stage of the permute
 // with identity maps — segments are "rows", keys "columns" below `key_limit` — and without the reference's value
 // ordering of duplicate columns (a CSR-constructor rule): equal keys keep their input order (tiles and row classes
@@ -3223,35 +3261,14 @@ extern "C" int sbx_permute_csr(sbx_handle_t h, sbx_index_type it, sbx_value_type
 // (sbx_convert.hip).  The caller has begun the arena.
 int sbx_sort_segments(sbx_handle_t h, int vb, int64_t nseg, int64_t key_limit, int64_t nnz, const int32_t *seg_ptr,
                       const int32_t *key_in, const char *val_in, int32_t *key_out, char *val_out) {
-  typedef int32_t I;
-  PermState *st = nullptr;
-  I *long_rows = nullptr, *block_rows = nullptr;
-  int2 *rec = nullptr;
-  const int block_cap = vb == 8 ? BlockRowCap<8>::value : BlockRowCap<4>::value;
-  unsigned long long *status = nullptr;
   sbx_aux_scope aux_scope(h);  // (the sort stage forks)
-  SBX_TRY(perm_prep_alloc(h, nseg, &st, &status, &rec));
-  SBX_TRY(sbx_salloc(h, (size_t)nseg, &long_rows));
-  SBX_TRY(sbx_salloc(h, (size_t)nseg * BR_CLASSES, &block_rows));
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_rowwise_prep<I>, dim3(sbx_grid_for((nseg + 3) / 4, 256, 8192)), dim3(256), seg_ptr,
-              (const I *)nullptr, nseg, (int64_t)0, nseg, rec);
-  I *sp = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)nseg + 1, &sp));
-  SBX_TRY(classify_and_scan<I>(h, (const int2 *)rec, (I *)nullptr, sp, nseg, long_rows, block_rows, nseg, block_cap, st,
-                               status));
-  PermState hs;
-  SBX_TRY(perm_fetch(h, &hs, st));
-  // (SBX_V_NONE: no value ordering of equal keys behind the sort)
-  if (vb == 0)
-    return sort_stage<I, 0>(h, SBX_V_NONE, (const int2 *)rec, key_in, val_in, (const I *)nullptr, seg_ptr, key_out, val_out,
-                         nseg, key_limit, nnz, long_rows, block_rows, nseg, hs, st, sp);
-  if (vb == 4)
-    return sort_stage<I, 4>(h, SBX_V_NONE, (const int2 *)rec, key_in, val_in, (const I *)nullptr, seg_ptr, key_out, val_out,
-                         nseg, key_limit, nnz, long_rows, block_rows, nseg, hs, st, sp);
-  return sort_stage<I, 8>(h, SBX_V_NONE, (const int2 *)rec, key_in, val_in, (const I *)nullptr, seg_ptr, key_out, val_out,
-                       nseg, key_limit, nnz, long_rows, block_rows, nseg, hs, st, sp);
+  PermCall<int32_t> c = {};
+  c.h = h, c.vt = SBX_V_NONE, c.vb = vb, c.m = key_limit;  // (SBX_V_NONE: no value ordering of equal keys behind the sort)
+  c.col_in = key_in, c.val_in = val_in, c.col_out = key_out, c.val_out = val_out;
+  return sort_rows_out_of_place(c, seg_ptr, nseg, nnz);
 }
 
+// A4: the CSR constructor's "if any row is unsorted, sort every row" in place.
 template <typename I>
 static int csr_sort_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, int64_t nnz, const void *row_ptr,
                                void *col, void *val) {
@@ -3265,36 +3282,13 @@ static int csr_sort_rows_typed(sbx_handle_t h, sbx_value_type vt, int64_t n, int
   SBX_REQUIRE(h, vb >= 0, "unknown value type");
   SBX_TRY(sbx_arena_begin(h));
   sbx_aux_scope aux_scope(h);  // (the sort stage forks)
-  PermState *st = nullptr;
-  I *long_rows = nullptr, *block_rows = nullptr, *ctmp = nullptr;
-  int2 *rec = nullptr;
-  const int block_cap = vb == 8 ? BlockRowCap<8>::value : BlockRowCap<4>::value;
-  char *vtmp = nullptr;
-  unsigned long long *status = nullptr;
-  SBX_TRY(perm_prep_alloc(h, n, &st, &status, &rec));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &long_rows));
-  SBX_TRY(sbx_salloc(h, (size_t)n * BR_CLASSES, &block_rows));
-  SBX_TRY(sbx_salloc(h, (size_t)nnz, &ctmp));
-  if (vb) SBX_TRY(sbx_salloc(h, (size_t)nnz * vb, &vtmp));
-  SBX_KLAUNCH(h, SBX_K_PERMUTE_PREP, k_rowwise_prep<I>, dim3(sbx_grid_for((n + 3) / 4, 256, 8192)), dim3(256),
-              (const I *)row_ptr, (const I *)nullptr, n, (int64_t)0, n, rec);
-  I *sp = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)n + 1, &sp));
-  SBX_TRY(classify_and_scan<I>(h, (const int2 *)rec, (I *)nullptr, sp, n, long_rows, block_rows, (int64_t)n, block_cap, st,
-                               status));
-  PermState hs;
-  SBX_TRY(perm_fetch(h, &hs, st));
-  int rc;
-#define STAGE(VBX)                                                                                               \
-  rc = sort_stage<I, VBX>(h, vt, (const int2 *)rec, (const I *)col, (const char *)val, (const I *)nullptr,          \
-                       (const I *)row_ptr, ctmp, vtmp, n, m, nnz, long_rows, block_rows, (int64_t)n, hs, st, sp)
-  if (vb == 0) STAGE(0);
-  else if (vb == 4) STAGE(4);
-  else STAGE(8);
-#undef STAGE
-  SBX_TRY(rc);
-  SBX_HIP(h, hipMemcpyAsync(col, ctmp, (size_t)nnz * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
-  if (vb) SBX_HIP(h, hipMemcpyAsync(val, vtmp, (size_t)nnz * vb, hipMemcpyDeviceToDevice, h->stream));
+  PermCall<I> c = {};
+  c.h = h, c.vt = vt, c.vb = vb, c.m = m, c.col_in = (const I *)col, c.val_in = (const char *)val;
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &c.col_out));
+  if (vb) SBX_TRY(sbx_salloc(h, (size_t)nnz * vb, &c.val_out));
+  SBX_TRY(sort_rows_out_of_place(c, (const I *)row_ptr, n, nnz));
+  SBX_HIP(h, hipMemcpyAsync(col, c.col_out, (size_t)nnz * sizeof(I), hipMemcpyDeviceToDevice, h->stream));
+  if (vb) SBX_HIP(h, hipMemcpyAsync(val, c.val_out, (size_t)nnz * vb, hipMemcpyDeviceToDevice, h->stream));
   return SBX_OK;
 }
 

@@ -513,7 +513,7 @@ def test_permute_long_rows_and_duplicates(ops, oracle):
     # a few very long rows (radix path), medium rows (bitonic path), duplicates with values
     g = np.random.default_rng(3)
     n, m = 64, 50000
-    # one row in every sort class: tile (<= 1024), block rows of 2048 / 4096 / 8192 slots, global radix
+    # one row in every sort class: tile (<= 128), block rows of 256 ... 8192 slots, long rows (segments / global radix)
     lens = np.array([0, 1, 2, 40, 33, 1024, 1025, 2048, 2049, 3000, 4096, 4097, 5000, 8192, 8193, 9000, 16384, 16385,
                      20000] + [int(x) for x in g.integers(0, 300, n - 19)])
     rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
