@@ -9,12 +9,16 @@
 //                   deg/resolution for dense rows (:384-395)
 // and the four band counters of :138-170 (nonzeros within m/128 of the diagonal,
 // split by sparse/dense class).  One O(nnz) pass, 4 B/nonzero + 16 B/row of traffic.
-// Three kernel families, chosen by what the matrix turns out to be (sbx_gray_row_keys below):
-//   k_gray_rows_short (+ k_gray_long_rows/finish, k_gray_list_medium)   banded / mesh matrices: 4 lanes per row
-//   k_gray_rows_tiny, k_gray_rows_listed (or k_gray_rows_balanced),    power-law matrices: a lane per row of up to 15
-//   k_gray_rows_medium, k_gray_units_finish                            entries, four per row of up to 64, longer rows cut
-//                                                                      into 1024-entry units
-//   k_gray_prep, k_gray_tile, k_gray_finish                             resolutions below 16: nonzero-parallel tiles
+// Three kernel families — banded / mesh matrices: 4 lanes per row; power-law matrices: a lane per row of up to 15
+// entries, four per row of up to 64, longer rows cut into 1024-entry units; nonzero-parallel tiles — and five routes,
+// chosen by what the matrix turns out to be (the entry point at the end of the file), in launch order:
+//   banded alone     gray_banded_attempt: k_gray_rows_short, read-back
+//   banded leftovers ... gray_banded_leftovers: k_gray_list_medium, k_gray_rows_medium, k_gray_units_finish (rows of 65 ..
+//                    8192 entries were met) and / or k_gray_long_rows, k_gray_long_finish (rows above), read-back
+//   power law        ... k_gray_rows_short stopped; gray_power_law: k_gray_rows_tiny, k_gray_rows_listed (or
+//                    k_gray_rows_balanced), k_gray_rows_medium, k_gray_units_finish, k_gray_fold, read-back
+//   tiles            gray_tiles: k_gray_prep, k_gray_tile, k_gray_finish, read-back (resolutions below 16); as the overflow
+//                    route after a k_gray_rows_short that listed more than 4096 rows above 8192 entries
 // The ordering stage (std::sort calls whose tie order is libstdc++-specific) stays
 // above the ABI in the host layer — see DESIGN.md "Gray".
 #include "sbx_device.h"
@@ -305,6 +309,28 @@ constexpr int GR_FLAG_OFF = 24 + GR_EARLY * 32;  // ... starting this many words
 constexpr int GR_SPREAD = 64;    // copies of the band counters the power-law kernels add to (4 GrayCounts = a 128-byte line each)
 constexpr unsigned GR_POWER_LAW = 2u;  // nlong[1]: 0 no row above GR_SHORT_MAX .. GR_MED_MAX met, 1 some, 2 many (start over)
 
+struct GrayLists {  // the unit lists' counters (the units themselves: "power-law matrices" below; units and slots are
+                    // reserved together: ONE add per workgroup; the mrows counter on a line of its own)
+  alignas(128) unsigned long long units_slots;  // low word: units listed, high word: partial slots handed out
+  alignas(128) unsigned n_mrows;
+};
+struct GrayBoth {  // band counters and the short-row kernel's long-row count: one read-back
+  GrayCounts c;
+  unsigned nlong, pad;  // pad: 0 / 1 / GR_POWER_LAW
+};
+struct GrayAll {  // everything the kernels count in: one allocation, one fill at the start of the call
+  GrayBoth b;
+  unsigned fill[24 - 2];
+  GrayCounts early[GR_EARLY * 4];  // k_gray_rows_short's counter copies (line i at &b.c + 4 + 4 i)
+  unsigned flags[GR_FLAGS * 32];
+  alignas(128) GrayCounts total2;  // the power-law route's counters (b.c holds what the stopped kernel left)
+  GrayLists lists;
+  alignas(128) unsigned mid_count;  // rows listed for k_gray_rows_listed
+  alignas(128) GrayCounts spread[GR_SPREAD * 4];
+};
+static_assert(offsetof(GrayAll, flags) == offsetof(GrayBoth, nlong) + GR_FLAG_OFF * 4 && offsetof(GrayAll, flags) % 128 == 0, "flag lines");
+static_assert(offsetof(GrayAll, early) == 4 * sizeof(GrayCounts), "the first counter copy sits one line behind the counters");
+
 // Exchange with lane ^ m inside a row's GR_LPR lanes.  m is a constant after unrolling: 1 and 2 are DPP quad permutations;
 // 4 is row_half_mirror (lane i <-> 7 - i of the 8) — the same partner QUAD, and every value exchanged here is
 // uniform inside a quad by then (both partners of a merge step compute the same symmetric result).  A DPP move is one
@@ -590,11 +616,7 @@ __global__ __launch_bounds__(256) void k_gray_rows_short(const X *__restrict__ r
 // k_gray_units_finish adds a row's slots up — plain stores, no atomics, no ordering between units.
 //   units[i] = (row, offset of the unit in the row, partial slot or -1, -)
 //   mrows[k] = (row, first partial slot, number of units, -)      rows of more than one unit
-constexpr int GU_SIZE = 1024;
-struct GrayLists {  // (units and slots are reserved together: ONE add per workgroup; the mrows counter on a line of its own)
-  alignas(128) unsigned long long units_slots;  // low word: units listed, high word: partial slots handed out
-  alignas(128) unsigned n_mrows;
-};
+constexpr int GU_SIZE = 1024;  // (the lists' counters: GrayLists above)
 // d[i] = length of row row_of(i) + lane if the row is to be listed, 0 otherwise (i < G).  Positions from wave scans and
 // one reservation per workgroup on the counters — every thread of the workgroup calls this, once: a workgroup's adds
 // to one line take ~7 ns each whatever else it does (4 K workgroups x 3 counters were most of a 109 us kernel).
@@ -1488,10 +1510,190 @@ extern "C" int sbx_gray_row_keys(sbx_handle_t h, sbx_index_type it, int64_t n, i
 #define SBX_GRAY_TINY_ROWS 1
 #endif
 
+namespace {
+
+// What every route of one call reads, computed once by the entry point; the routes take it by reference.
+struct GrayCall {
+  sbx_handle_t h;
+  int64_t n, m, nnz;
+  const X *rp, *cl;
+  X *degree_out;
+  unsigned long long *keys;
+  int bits, nnz_threshold;  // bits: the resolution, clamped to m
+  uint32_t width, magic, band;  // block width m / bits (:210); c / width = umulhi(c, magic) or that + 1 (c < 2^31); m / 128 (:138)
+  int wshift, lv;  // log2(width), -1 if that is no power of two; counter levels a row of up to GR_SHORT_MAX entries needs
+  GrayAll *all;    // on the device, zeroed at the start of the call; counts(): what the banded and the tile routes add to
+  int32_t *long_list;  // the rows above GR_MED_MAX entries k_gray_rows_short lists, GR_LONG_LIST at most
+  int4 *units, *mrows;  // alloc_units: the lists of k_gray_rows_medium and k_gray_units_finish (their counters: all->lists)
+  unsigned *partial;    // ... and the partial slots of rows of several units
+  GrayCounts *counts() const { return &all->b.c; }
+  int shift_or_0() const { return wshift >= 0 ? wshift : 0; }  // k_gray_rows_medium gets wshift as it is, the others this
+};
+
+// Where a run-time property of the call becomes a template argument (as with_value_bytes in sbx_permute.hip): is the
+// block width a power of two — f(std::true_type / false_type) —, the row kernels' bitmap type and counter levels — f(B(), LV)
+template <typename F>
+void with_pow2(const GrayCall &c, F &&f) {
+  if (c.wshift >= 0) f(std::true_type()); else f(std::false_type());
+}
+template <typename F>
+void with_shape(const GrayCall &c, F &&f) {
+  if (c.bits > 32 && c.lv <= 1) f(0ull, std::integral_constant<int, 1>());
+  else if (c.bits > 32) f(0ull, std::integral_constant<int, 2>());  // 64 blocks: thr <= 64 / 64
+  else if (c.lv <= 1) f(uint32_t(), std::integral_constant<int, 1>());
+  else if (c.lv <= 3) f(uint32_t(), std::integral_constant<int, 3>());
+  else f(uint32_t(), std::integral_constant<int, 5>());
+}
+
+// ---- the launches that depend on them, each written once; `counts`: what the launch adds to ----
+void launch_rows_short(const GrayCall &c, unsigned grid) {
+  with_shape(c, [&](auto b, auto lv) { with_pow2(c, [&](auto p) {
+    SBX_KLAUNCH(c.h, SBX_K_GRAY, (k_gray_rows_short<decltype(b), decltype(lv)::value, decltype(p)::value>), dim3(grid),
+                dim3(256), c.rp, c.cl, c.n, c.width, c.magic, c.band, c.shift_or_0(), c.bits, c.nnz_threshold, c.degree_out,
+                c.keys, c.counts(), &c.all->b.nlong, c.long_list);
+  }); });
+}
+void launch_rows_balanced(const GrayCall &c, unsigned grid, GrayCounts *counts) {
+  with_shape(c, [&](auto b, auto lv) { with_pow2(c, [&](auto p) {
+    SBX_KLAUNCH(c.h, SBX_K_GRAY, (k_gray_rows_balanced<decltype(b), decltype(lv)::value, decltype(p)::value>), dim3(grid),
+                dim3(256), c.rp, c.cl, c.n, c.width, c.magic, c.band, c.shift_or_0(), c.bits, c.nnz_threshold, c.degree_out,
+                c.keys, counts, &c.all->b.nlong, c.long_list, c.units, c.mrows, &c.all->lists);
+  }); });
+}
+void launch_rows_tiny_listed(const GrayCall &c, unsigned grid, GrayCounts *counts, int32_t *mid_list) {  // (a pair)
+  with_shape(c, [&](auto b, auto lv) { with_pow2(c, [&](auto p) {
+    SBX_KLAUNCH(c.h, SBX_K_GRAY, (k_gray_rows_tiny<decltype(b), decltype(p)::value>), dim3(grid), dim3(256), c.rp, c.cl, c.n,
+                (int32_t)c.nnz, c.width, c.magic, c.band, c.shift_or_0(), c.nnz_threshold, c.degree_out, c.keys, counts,
+                c.units, c.mrows, &c.all->lists, mid_list, &c.all->mid_count);
+    SBX_KLAUNCH(c.h, SBX_K_GRAY, (k_gray_rows_listed<decltype(b), decltype(lv)::value, decltype(p)::value>),
+                dim3((unsigned)c.h->num_cus * 8), dim3(256), c.rp, c.cl, (const int32_t *)mid_list,
+                (const unsigned *)&c.all->mid_count, (int32_t)c.nnz, c.width, c.magic, c.band, c.shift_or_0(), c.bits,
+                c.nnz_threshold, c.degree_out, c.keys, counts);
+  }); });
+}
+void launch_rows_medium(const GrayCall &c, GrayCounts *counts, unsigned nspread) {  // nspread copies of `counts`, a line each
+  with_pow2(c, [&](auto p) {
+    SBX_KLAUNCH(c.h, SBX_K_GRAY, k_gray_rows_medium<decltype(p)::value>, dim3((unsigned)c.h->num_cus * 8), dim3(256), c.rp,
+                c.cl, (const int4 *)c.units, (const GrayLists *)&c.all->lists, c.width, c.magic, c.wshift, c.band, c.bits,
+                c.nnz_threshold, (int32_t)c.nnz, c.degree_out, c.keys, c.partial, counts, nspread);
+  });
+}
+void launch_units_finish(const GrayCall &c, unsigned grid, GrayCounts *counts, unsigned nspread) {
+  SBX_KLAUNCH(c.h, SBX_K_GRAY, k_gray_units_finish, dim3(grid), dim3(256), c.rp, (const int4 *)c.mrows,
+              (const GrayLists *)&c.all->lists, (const unsigned *)c.partial, c.bits, c.nnz_threshold, c.degree_out, c.keys,
+              counts, nspread);
+}
+int alloc_units(GrayCall &c) {
+  // a row above GR_SHORT_MAX entries is at least one unit, every further unit is GU_SIZE entries of it; a row of k > 1
+  // units has more than (k - 1) GU_SIZE entries, and k <= 2 (k - 1)
+  const size_t per_size = (size_t)(c.nnz / GU_SIZE), per_row = (size_t)(c.nnz / (GR_SHORT_MAX + 1));
+  SBX_TRY(sbx_salloc(c.h, (per_row < (size_t)c.n ? per_row : (size_t)c.n) + per_size + 1, &c.units));
+  SBX_TRY(sbx_salloc(c.h, per_size + 1, &c.mrows));
+  return sbx_salloc(c.h, (2 * per_size + 2) * GU_SLOT, &c.partial);
+}
+void store_counts(int64_t *counts_host, const GrayCounts &c) {
+  counts_host[0] = (int64_t)c.nnz_sparse, counts_host[1] = (int64_t)c.diag_sparse;
+  counts_host[2] = (int64_t)c.nnz_dense, counts_host[3] = (int64_t)c.diag_dense;
+}
+
+// one read-back for the banded routes: how many long rows k_gray_rows_short met, its flag, and the band counters — what
+// the later kernels added to b.c + k_gray_rows_short's GR_EARLY copies, summed here
+int fetch_both(const GrayCall &c, GrayBoth *hb) {
+  GrayAll head;  // (filled up to the flag lines)
+  SBX_TRY(sbx_readback(c.h, &head, c.all, offsetof(GrayAll, flags)));
+  *hb = head.b;
+  for (int i = 0; i < GR_EARLY; i++)
+    for (int k = 0; k < 4; k++) (&hb->c.nnz_sparse)[k] += (&head.early[4 * i].nnz_sparse)[k];
+  return SBX_OK;
+}
+
+// The routes.  The banded kernel, tried first: it lists the rows above GR_MED_MAX entries, flags rows of GR_SHORT_MAX + 1 ..
+// GR_MED_MAX (hb->pad = 1) and stops in the body of a power-law distribution (GR_POWER_LAW); final if it met no such row.
+int gray_banded_attempt(const GrayCall &c, GrayBoth *hb) {
+  launch_rows_short(c, sbx_grid_for(c.n, 256 / GR_LPR, (int64_t)c.h->num_cus * 16));
+  SBX_LAUNCH_CHECK(c.h);
+  return fetch_both(c, hb);
+}
+
+// The banded kernel stopped (or was not tried): start over with the kernels that cost per entry; one read-back, at the end.
+int gray_power_law(GrayCall &c, GrayBoth *hb) {
+  SBX_TRY(alloc_units(c));
+  GrayCounts *spread = c.all->spread;
+  const int64_t brows = (int64_t)GB_ITERS * 4 * GB_GROUPS * 64;  // rows per workgroup
+  const unsigned bgrid = (unsigned)((c.n + brows - 1) / brows);
+  // (a row of up to GR_TINY entries has threshold 0 when it is shorter than `resolution` or not above the nnz threshold)
+  if (SBX_GRAY_TINY_ROWS && (c.bits > GR_TINY || c.nnz_threshold >= GR_TINY)) {
+    int32_t *mid_list = nullptr;
+    SBX_TRY(sbx_salloc(c.h, (size_t)c.n, &mid_list));
+    launch_rows_tiny_listed(c, bgrid, spread, mid_list);
+  } else {
+    launch_rows_balanced(c, bgrid, spread);
+  }
+  launch_rows_medium(c, spread, (unsigned)GR_SPREAD);
+  launch_units_finish(c, (unsigned)c.h->num_cus * 4, spread, (unsigned)GR_SPREAD);
+  SBX_KLAUNCH(c.h, SBX_K_GRAY, k_gray_fold, dim3(1), dim3(64), (const GrayCounts *)spread, &c.all->total2);
+  SBX_LAUNCH_CHECK(c.h);
+  hb->nlong = hb->pad = 0;
+  return sbx_readback(c.h, &hb->c, &c.all->total2, sizeof(GrayCounts));
+}
+
+// What the banded kernel left: a few rows of GR_SHORT_MAX + 1 .. GR_MED_MAX entries (hb->pad: listed, then a wave per
+// unit) and up to GR_LONG_LIST rows above (boundary rows of a clamped band, a few hubs: GR_PARTS workgroups each).
+int gray_banded_leftovers(GrayCall &c, GrayBoth *hb) {
+  sbx_handle_t h = c.h;
+  const unsigned hlong = hb->nlong, *nlong = &c.all->b.nlong;
+  if (hb->pad) {
+    SBX_TRY(alloc_units(c));
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_list_medium, dim3((unsigned)((c.n + GL_ROWS - 1) / GL_ROWS)), dim3(256), c.rp, c.n,
+                c.units, c.mrows, &c.all->lists);
+    launch_rows_medium(c, c.counts(), 1u);
+    launch_units_finish(c, 64u, c.counts(), 1u);
+  }
+  if (hlong) {
+    unsigned *slots = nullptr;
+    SBX_TRY(sbx_salloc(h, (size_t)hlong * 65, &slots));
+    SBX_HIP(h, hipMemsetAsync(slots, 0, sizeof(unsigned) * (size_t)hlong * 65, h->stream));
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_long_rows, dim3(hlong * GR_PARTS), dim3(256), c.rp, c.cl,
+                (const int32_t *)c.long_list, nlong, c.width, c.magic, c.band, slots);
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_long_finish, dim3((hlong + 3) / 4), dim3(256), c.rp, (const int32_t *)c.long_list,
+                nlong, (const unsigned *)slots, c.bits, c.nnz_threshold, c.degree_out, c.keys, c.counts());
+  }
+  SBX_LAUNCH_CHECK(h);
+  return fetch_both(c, hb);
+}
+
+// The tile kernels: resolutions the row kernels are not built for, and matrices whose long-row list overflowed.
+int gray_tiles(const GrayCall &c, GrayCounts *total) {
+  sbx_handle_t h = c.h;
+  const int64_t ntiles = (c.nnz + GT_TILE - 1) / GT_TILE;
+  int32_t *fix_row = nullptr, *tile_row = nullptr;
+  unsigned *slot_acc = nullptr, *tile_counts = nullptr;
+  SBX_TRY(sbx_salloc(h, ntiles + 1, &fix_row));
+  SBX_TRY(sbx_salloc(h, ntiles + 1, &tile_row));
+  SBX_TRY(sbx_salloc(h, (ntiles + 1) * 64, &slot_acc));
+  SBX_TRY(sbx_salloc(h, (ntiles + 1) * 4, &tile_counts));
+  SBX_HIP(h, hipMemsetAsync(fix_row, 0xFF, (size_t)(ntiles + 1) * sizeof(int32_t), h->stream));
+  SBX_HIP(h, hipMemsetAsync(slot_acc, 0, (size_t)(ntiles + 1) * 64 * sizeof(unsigned), h->stream));
+  const int64_t prep_items = c.n > ntiles + 1 ? c.n : ntiles + 1;
+  SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_prep, dim3(sbx_grid_for(prep_items, 256, (int64_t)h->num_cus * 16)), dim3(256), c.rp,
+              c.n, c.nnz, ntiles, c.degree_out, c.keys, tile_row);
+  if (ntiles > 0) {
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_tile, dim3((unsigned)ntiles), dim3(GT_THREADS), c.rp, c.cl, c.nnz,
+                (const int32_t *)tile_row, c.width, c.magic, c.band, c.bits, c.nnz_threshold, c.keys, fix_row, slot_acc,
+                tile_counts);
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_finish, dim3(sbx_grid_for(ntiles, 256, (int64_t)h->num_cus)), dim3(256), c.rp, c.bits,
+                c.nnz_threshold, (const int32_t *)fix_row, (const unsigned *)slot_acc, (const unsigned *)tile_counts, ntiles,
+                c.keys, c.counts());
+  }
+  SBX_LAUNCH_CHECK(h);
+  return sbx_readback(h, total, c.counts(), sizeof(GrayCounts));
+}
+
+}  // namespace
+
 int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void *row_ptr, const void *col, int resolution,
                    int nnz_threshold, void *degree_out, uint64_t *key_out, int64_t *counts_host) {
-  int bits = resolution;
-  if (m < bits) bits = (int)m;  // gray_reorder.cc:206-208
+  const int bits = sbx_gray_bits(resolution, m);
   if (bits <= 0 || bits > 64) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbx_gray_row_keys: resolution must be in 1..64");
   const int64_t width = m / bits;  // :210
   if (width * bits != m)
@@ -1499,242 +1701,34 @@ int SBX_GRAY_ENTRY(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, const void
              "sbx_gray_row_keys: m=%lld is not a multiple of the resolution %d (the reference indexes its "
              "bucket array out of bounds there, gray_reorder.cc:251)", (long long)m, bits);
   SBX_TRY(sbx_arena_begin(h));
-  counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
+  GrayBoth hb = {{0, 0, 0, 0}, 0, GR_POWER_LAW};  // what the banded kernel reports; not tried: as if it had stopped
+  store_counts(counts_host, hb.c);
   if (n == 0) return SBX_OK;
-  struct GrayBoth {  // band counters and the short-row kernel's long-row count: one fill, one read-back
-    GrayCounts c;
-    unsigned nlong, pad;  // pad: 0 / 1 / GR_POWER_LAW
-  };
-  struct GrayAll {  // everything the kernels count in: one fill at the start of the call
-    GrayBoth b;
-    unsigned fill[24 - 2];
-    GrayCounts early[GR_EARLY * 4];  // k_gray_rows_short's counter copies (line i at &b.c + 4 + 4 i)
-    unsigned flags[GR_FLAGS * 32];
-    alignas(128) GrayCounts total2;  // the power-law path's counters (b.c holds what the stopped kernel left)
-    GrayLists lists;
-    alignas(128) unsigned mid_count;  // rows listed for k_gray_rows_listed
-    alignas(128) GrayCounts spread[GR_SPREAD * 4];
-  };
-  static_assert(offsetof(GrayAll, flags) == offsetof(GrayBoth, nlong) + GR_FLAG_OFF * 4 && offsetof(GrayAll, flags) % 128 == 0, "flag lines");
-  static_assert(offsetof(GrayAll, early) == 4 * sizeof(GrayCounts), "the first counter copy sits one line behind the counters");
-  GrayAll *all = nullptr;
-  SBX_TRY(sbx_salloc(h, 1, &all));
-  SBX_HIP(h, hipMemsetAsync(all, 0, sizeof(GrayAll), h->stream));
-  GrayBoth *both = &all->b;
-  GrayCounts *cnt = &both->c;
-  const int64_t band = m / 128;  // :138
-  // c / width = umulhi(c, magic) or that + 1 (c < 2^31): magic = floor(2^32 / width), saturated for width 1
-  const uint64_t mg = ((uint64_t)1 << 32) / (uint64_t)width;
-  const uint32_t magic = mg > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)mg;
-  const X *rp = (const X *)row_ptr, *cl = (const X *)col;
-  unsigned long long *keys = (unsigned long long *)key_out;
-  {
-    // short-row fast path, tried first: the kernel lists the rows above GR_SHORT_MAX entries it meets; up to
-    // GR_LONG_LIST of them (boundary rows of a clamped band, a few hubs) then get GR_PARTS workgroups each
-    unsigned *nlong = &both->nlong;
-    int32_t *long_list = nullptr;
-    SBX_TRY(sbx_salloc(h, (size_t)GR_LONG_LIST, &long_list));
-    const unsigned hmax = (unsigned)GR_SHORT_MAX;  // bound of the rows the kernel handles
-    // a row of d <= hmax entries compares its block counts with d / resolution <= hmax / resolution: that many
-    // saturating counter slices + 1.  The kernel is built for up to 5 (resolution >= 16) — what the tests of round 2
-    // missed and tools/fuzz_ops.py found: below that the tile kernel does the work
-    const int lv = (int)(hmax >= (unsigned)bits && (int)hmax > nnz_threshold ? hmax / (unsigned)bits : 0u) + 1;
-    if (SBX_GRAY_SHORT_ROWS && lv <= (bits <= 32 ? 5 : 2) && nnz >= 4) {  // (gr_load4 reads 16 bytes at a clamped address)
-      const unsigned grid = sbx_grid_for(n, 256 / GR_LPR, (int64_t)h->num_cus * 16);
-      int wshift = -1;
-      if ((width & (width - 1)) == 0)
-        for (wshift = 0; ((int64_t)1 << wshift) < width; wshift++) {}
-#define GRAY_ROWS(K, GRID, B, LV, ...)                                                                              \
-  do {                                                                                                             \
-    if (wshift >= 0)                                                                                               \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (K<B, LV, true>), dim3(GRID), dim3(256), rp, cl, n, (uint32_t)width, magic,        \
-                  (uint32_t)band, wshift, bits, nnz_threshold, (X *)degree_out, keys, cnt, nlong, long_list,  \
-                  ##__VA_ARGS__);                                                                                  \
-    else                                                                                                           \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (K<B, LV, false>), dim3(GRID), dim3(256), rp, cl, n, (uint32_t)width, magic,       \
-                  (uint32_t)band, 0, bits, nnz_threshold, (X *)degree_out, keys, cnt, nlong, long_list,       \
-                  ##__VA_ARGS__);                                                                                  \
-  } while (0)
-#define GRAY_ROWS_BY_LEVELS(K, GRID, ...)                                                                           \
-  do {                                                                                                             \
-    if (bits <= 32) {                                                                                              \
-      if (lv <= 1) GRAY_ROWS(K, GRID, uint32_t, 1, ##__VA_ARGS__);                                                 \
-      else if (lv <= 3) GRAY_ROWS(K, GRID, uint32_t, 3, ##__VA_ARGS__);                                            \
-      else GRAY_ROWS(K, GRID, uint32_t, 5, ##__VA_ARGS__);                                                         \
-    } else {                                                                                                       \
-      if (lv <= 1) GRAY_ROWS(K, GRID, unsigned long long, 1, ##__VA_ARGS__);                                       \
-      else GRAY_ROWS(K, GRID, unsigned long long, 2, ##__VA_ARGS__); /* 64 blocks: thr <= 64 / 64 */               \
-    }                                                                                                              \
-  } while (0)
-      GrayBoth hb;
-      hb.nlong = 0, hb.pad = GR_POWER_LAW;
-      // the counters (what the later kernels of the banded path added) + k_gray_rows_short's GR_EARLY copies, summed here
-      auto fetch_both = [&]() -> int {
-        struct { GrayBoth b; unsigned fill[24 - 2]; GrayCounts early[GR_EARLY * 4]; } head;
-        static_assert(sizeof(head) == offsetof(GrayAll, flags), "the head of GrayAll");
-        SBX_TRY(sbx_readback(h, &head, all, sizeof(head)));
-        hb = head.b;
-        for (int i = 0; i < GR_EARLY; i++) {
-          hb.c.nnz_sparse += head.early[4 * i].nnz_sparse, hb.c.diag_sparse += head.early[4 * i].diag_sparse;
-          hb.c.nnz_dense += head.early[4 * i].nnz_dense, hb.c.diag_dense += head.early[4 * i].diag_dense;
-        }
-        return SBX_OK;
-      };
-      if (SBX_GRAY_BANDED_FIRST) {
-        GRAY_ROWS_BY_LEVELS(k_gray_rows_short, grid);
-        SBX_LAUNCH_CHECK(h);
-        // one read-back: how many long rows the kernel met and — final if there were none — the band counters
-        SBX_TRY(fetch_both());
-      }
-      const int wsh = wshift >= 0 ? wshift : -1;
-      // the lists of k_gray_rows_medium: a row above GR_SHORT_MAX entries is at least one unit, every further unit is
-      // GU_SIZE entries of it; a row of k > 1 units has more than (k - 1) GU_SIZE entries, and k <= 2 (k - 1)
-      const size_t max_units = (size_t)(nnz / (GR_SHORT_MAX + 1) < n ? nnz / (GR_SHORT_MAX + 1) : n) + (size_t)(nnz / GU_SIZE) + 1;
-      const size_t max_slots = 2 * (size_t)(nnz / GU_SIZE) + 2, max_mrows = (size_t)(nnz / GU_SIZE) + 1;
-      int4 *units = nullptr, *mrows = nullptr;
-      GrayLists *lc = nullptr;
-      unsigned *partial = nullptr;
-#define GRAY_MEDIUM(COUNTS, NSPREAD)                                                                                 \
-  do {                                                                                                             \
-    if (wshift >= 0)                                                                                               \
-      SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_rows_medium<true>, dim3((unsigned)h->num_cus * 8), dim3(256), rp, cl,       \
-                  (const int4 *)units, (const GrayLists *)lc, (uint32_t)width, magic, wsh, (uint32_t)band, bits,     \
-                  nnz_threshold, (int32_t)nnz, (X *)degree_out, keys, partial, COUNTS, NSPREAD);              \
-    else                                                                                                           \
-      SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_rows_medium<false>, dim3((unsigned)h->num_cus * 8), dim3(256), rp, cl,      \
-                  (const int4 *)units, (const GrayLists *)lc, (uint32_t)width, magic, wsh, (uint32_t)band, bits,     \
-                  nnz_threshold, (int32_t)nnz, (X *)degree_out, keys, partial, COUNTS, NSPREAD);              \
-  } while (0)
-      auto alloc_lists = [&]() -> int {
-        SBX_TRY(sbx_salloc(h, max_units, &units));
-        SBX_TRY(sbx_salloc(h, max_mrows, &mrows));
-        SBX_TRY(sbx_salloc(h, max_slots * GU_SLOT, &partial));
-        lc = &all->lists;  // (zeroed with the rest at the start of the call)
-        return SBX_OK;
-      };
-      if (hb.pad == GR_POWER_LAW) {
-        // the kernel found the body of a power-law degree distribution and stopped (or was not tried): start over
-        // with the kernels that cost per entry; no read-back until the end
-        SBX_TRY(alloc_lists());
-        GrayCounts *spread = all->spread;
-        const int64_t brows = (int64_t)GB_ITERS * 4 * GB_GROUPS * 64;  // rows per workgroup
-        const unsigned bgrid = (unsigned)((n + brows - 1) / brows);
-        // (a row of up to GR_TINY entries has threshold 0 when it is shorter than `resolution` or not above the nnz threshold)
-        if (SBX_GRAY_TINY_ROWS && (bits > GR_TINY || nnz_threshold >= GR_TINY)) {
-          int32_t *mid_list = nullptr;
-          SBX_TRY(sbx_salloc(h, (size_t)n, &mid_list));
-#define GRAY_TINY(B)                                                                                                  \
-  do {                                                                                                               \
-    if (wshift >= 0)                                                                                                 \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (k_gray_rows_tiny<B, true>), dim3(bgrid), dim3(256), rp, cl, n, (int32_t)nnz,        \
-                  (uint32_t)width, magic, (uint32_t)band, wshift, nnz_threshold, (X *)degree_out, keys, spread, \
-                  units, mrows, lc, mid_list, &all->mid_count);                                                      \
-    else                                                                                                             \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (k_gray_rows_tiny<B, false>), dim3(bgrid), dim3(256), rp, cl, n, (int32_t)nnz,       \
-                  (uint32_t)width, magic, (uint32_t)band, 0, nnz_threshold, (X *)degree_out, keys, spread, units, \
-                  mrows, lc, mid_list, &all->mid_count);                                                             \
-  } while (0)
-          if (bits <= 32) GRAY_TINY(uint32_t);
-          else GRAY_TINY(unsigned long long);
-#undef GRAY_TINY
-#define GRAY_LISTED(B, LV)                                                                                            \
-  do {                                                                                                               \
-    if (wshift >= 0)                                                                                                 \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (k_gray_rows_listed<B, LV, true>), dim3((unsigned)h->num_cus * 8), dim3(256), rp, cl, \
-                  (const int32_t *)mid_list, (const unsigned *)&all->mid_count, (int32_t)nnz, (uint32_t)width, magic, \
-                  (uint32_t)band, wshift, bits, nnz_threshold, (X *)degree_out, keys, spread);                 \
-    else                                                                                                             \
-      SBX_KLAUNCH(h, SBX_K_GRAY, (k_gray_rows_listed<B, LV, false>), dim3((unsigned)h->num_cus * 8), dim3(256), rp,   \
-                  cl, (const int32_t *)mid_list, (const unsigned *)&all->mid_count, (int32_t)nnz, (uint32_t)width,   \
-                  magic, (uint32_t)band, 0, bits, nnz_threshold, (X *)degree_out, keys, spread);               \
-  } while (0)
-          if (bits <= 32) {
-            if (lv <= 1) GRAY_LISTED(uint32_t, 1);
-            else if (lv <= 3) GRAY_LISTED(uint32_t, 3);
-            else GRAY_LISTED(uint32_t, 5);
-          } else {
-            if (lv <= 1) GRAY_LISTED(unsigned long long, 1);
-            else GRAY_LISTED(unsigned long long, 2);
-          }
-#undef GRAY_LISTED
-        } else {
-          GrayCounts *cnt = spread;  // (what the launch macro passes as the counters)
-          GRAY_ROWS_BY_LEVELS(k_gray_rows_balanced, bgrid, units, mrows, lc);
-        }
-        GRAY_MEDIUM(spread, (unsigned)GR_SPREAD);
-        SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_units_finish, dim3((unsigned)h->num_cus * 4), dim3(256), rp,
-                    (const int4 *)mrows, (const GrayLists *)lc, (const unsigned *)partial, bits, nnz_threshold,
-                    (X *)degree_out, keys, spread, (unsigned)GR_SPREAD);
-        SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_fold, dim3(1), dim3(64), (const GrayCounts *)spread, &all->total2);
-        SBX_LAUNCH_CHECK(h);
-        SBX_TRY(sbx_readback(h, &hb.c, &all->total2, sizeof(GrayCounts)));
-        hb.nlong = 0, hb.pad = 0;
-      } else if (hb.nlong <= (unsigned)GR_LONG_LIST && (hb.nlong || hb.pad)) {
-        const unsigned hlong = hb.nlong;
-        if (hb.pad) {  // a few rows of GR_SHORT_MAX + 1 .. GR_MED_MAX entries: listed, then a wave per unit
-          SBX_TRY(alloc_lists());
-          SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_list_medium, dim3((unsigned)((n + GL_ROWS - 1) / GL_ROWS)), dim3(256), rp, n,
-                      units, mrows, lc);
-          GRAY_MEDIUM(cnt, 1u);
-          SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_units_finish, dim3(64), dim3(256), rp, (const int4 *)mrows,
-                      (const GrayLists *)lc, (const unsigned *)partial, bits, nnz_threshold, (X *)degree_out, keys,
-                      cnt, 1u);
-        }
-        if (hlong) {
-          unsigned *slots = nullptr;
-          SBX_TRY(sbx_salloc(h, (size_t)hlong * 65, &slots));
-          SBX_HIP(h, hipMemsetAsync(slots, 0, sizeof(unsigned) * (size_t)hlong * 65, h->stream));
-          SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_long_rows, dim3(hlong * GR_PARTS), dim3(256), rp, cl,
-                      (const int32_t *)long_list, (const unsigned *)nlong, (uint32_t)width, magic, (uint32_t)band, slots);
-          SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_long_finish, dim3((hlong + 3) / 4), dim3(256), rp,
-                      (const int32_t *)long_list, (const unsigned *)nlong, (const unsigned *)slots, bits, nnz_threshold,
-                      (X *)degree_out, keys, cnt);
-        }
-        SBX_LAUNCH_CHECK(h);
-        SBX_TRY(fetch_both());
-      }
-#undef GRAY_MEDIUM
-#undef GRAY_ROWS_BY_LEVELS
-#undef GRAY_ROWS
-      if (hb.nlong <= (unsigned)GR_LONG_LIST) {  // (the power-law path lists nothing there)
-        SBX_PROF_BYTES(h, SBX_K_GRAY, 4 * nnz + 16 * n + 4);
-        counts_host[0] = (int64_t)hb.c.nnz_sparse;
-        counts_host[1] = (int64_t)hb.c.diag_sparse;
-        counts_host[2] = (int64_t)hb.c.nnz_dense;
-        counts_host[3] = (int64_t)hb.c.diag_dense;
-        return SBX_OK;
-      }
-      // more rows above GR_MED_MAX entries than the list holds: start over with the tile kernel
-      SBX_HIP(h, hipMemsetAsync(cnt, 0, sizeof(GrayCounts), h->stream));
+  GrayCall c = {h, n, m, nnz, (const X *)row_ptr, (const X *)col, (X *)degree_out, (unsigned long long *)key_out, bits, nnz_threshold};
+  c.width = (uint32_t)width, c.band = (uint32_t)(m / 128), c.wshift = -1;
+  const uint64_t mg = ((uint64_t)1 << 32) / (uint64_t)width;  // floor(2^32 / width), saturated for width 1
+  c.magic = mg > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)mg;
+  if ((width & (width - 1)) == 0)
+    for (c.wshift = 0; ((int64_t)1 << c.wshift) < width; c.wshift++) {}
+  // a row of d <= GR_SHORT_MAX entries compares its block counts with d / resolution: that many saturating counter slices
+  // + 1.  The row kernels are built for up to 5 (resolution >= 16; tools/fuzz_ops.py found that bound): else the tiles
+  c.lv = (GR_SHORT_MAX >= bits && GR_SHORT_MAX > nnz_threshold ? GR_SHORT_MAX / bits : 0) + 1;
+  SBX_TRY(sbx_salloc(h, 1, &c.all));
+  SBX_HIP(h, hipMemsetAsync(c.all, 0, sizeof(GrayAll), h->stream));
+  SBX_TRY(sbx_salloc(h, (size_t)GR_LONG_LIST, &c.long_list));
+  if (SBX_GRAY_SHORT_ROWS && c.lv <= (bits <= 32 ? 5 : 2) && nnz >= 4) {  // (gr_load4 reads 16 bytes at a clamped address)
+    if (SBX_GRAY_BANDED_FIRST) SBX_TRY(gray_banded_attempt(c, &hb));
+    if (hb.pad == GR_POWER_LAW) SBX_TRY(gray_power_law(c, &hb));
+    else if (hb.nlong <= (unsigned)GR_LONG_LIST && (hb.nlong || hb.pad)) SBX_TRY(gray_banded_leftovers(c, &hb));
+    if (hb.nlong <= (unsigned)GR_LONG_LIST) {  // (the banded kernel alone, or with one of the two above)
+      SBX_PROF_BYTES(h, SBX_K_GRAY, 4 * nnz + 16 * n + 4);
+      store_counts(counts_host, hb.c);
+      return SBX_OK;
     }
+    // more rows above GR_MED_MAX entries than the list holds: start over with the tile kernels
+    SBX_HIP(h, hipMemsetAsync(c.counts(), 0, sizeof(GrayCounts), h->stream));
   }
-  const int64_t ntiles = (nnz + GT_TILE - 1) / GT_TILE;
-  int32_t *fix_row = nullptr, *tile_row = nullptr;
-  unsigned *slot_acc = nullptr;
-  SBX_TRY(sbx_salloc(h, ntiles + 1, &fix_row));
-  SBX_TRY(sbx_salloc(h, ntiles + 1, &tile_row));
-  SBX_TRY(sbx_salloc(h, (ntiles + 1) * 64, &slot_acc));
-  unsigned *tile_counts = nullptr;
-  SBX_TRY(sbx_salloc(h, (ntiles + 1) * 4, &tile_counts));
-  SBX_HIP(h, hipMemsetAsync(fix_row, 0xFF, (size_t)(ntiles + 1) * sizeof(int32_t), h->stream));
-  SBX_HIP(h, hipMemsetAsync(slot_acc, 0, (size_t)(ntiles + 1) * 64 * sizeof(unsigned), h->stream));
-  const int64_t prep_items = n > ntiles + 1 ? n : ntiles + 1;
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_prep, dim3(sbx_grid_for(prep_items, 256, (int64_t)h->num_cus * 16)), dim3(256),
-              rp, n, nnz, ntiles, (X *)degree_out, keys, tile_row);
-  if (ntiles > 0) {
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_tile, dim3((unsigned)ntiles), dim3(GT_THREADS), rp, cl, nnz,
-                (const int32_t *)tile_row, (uint32_t)width, magic, (uint32_t)band, bits, nnz_threshold, keys, fix_row,
-                slot_acc, tile_counts);
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_gray_finish, dim3(sbx_grid_for(ntiles, 256, (int64_t)h->num_cus)), dim3(256),
-                rp, bits, nnz_threshold, (const int32_t *)fix_row, (const unsigned *)slot_acc,
-                (const unsigned *)tile_counts, ntiles, keys, cnt);
-  }
-  SBX_LAUNCH_CHECK(h);
-  GrayCounts hc;
-  SBX_TRY(sbx_readback(h, &hc, cnt, sizeof(GrayCounts)));
-  counts_host[0] = (int64_t)hc.nnz_sparse;
-  counts_host[1] = (int64_t)hc.diag_sparse;
-  counts_host[2] = (int64_t)hc.nnz_dense;
-  counts_host[3] = (int64_t)hc.diag_dense;
+  SBX_TRY(gray_tiles(c, &hb.c));
+  store_counts(counts_host, hb.c);
   return SBX_OK;
 }

@@ -149,129 +149,138 @@ __global__ __launch_bounds__(256) void k_go_widen(const uint32_t *__restrict__ i
   for (; i < n; i += stride) out[i] = (I)in[i];
 }
 
+// What both forms of a call read: the entry point's six, what gray_order_typed derives once, gray_order_scratch's buffers
 template <typename I>
-int gray_order_one_sort(sbx_handle_t h, int64_t n, const I *deg, const uint64_t *gkey, bool sparse_banded, bool dense_banded,
-                        int kbits, int dbits, int cbits, uint32_t dense_class, int64_t dmax, int64_t thr, int group_size,
-                        uint64_t mask, I *inv_out) {
-  const unsigned grid = sbx_grid_for(n, 256, (int64_t)h->num_cus * 16);
-  uint32_t *ia = nullptr, *ib = nullptr, *present = nullptr, *rank = nullptr, *section = nullptr;
-  uint64_t *qa = nullptr, *qb = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ia));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ib));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &qa));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &qb));
-  SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &section));
-  if (!sparse_banded && dmax > 0) {  // the sections of the degrees (a "highly banded" sparse class has none)
-    SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &present));
-    SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &rank));
-    SBX_HIP(h, hipMemsetAsync(present, 0, sizeof(uint32_t) * (size_t)(dmax + 2), h->stream));
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_present<I>, dim3(grid), dim3(256), deg, n, thr, present);
-    SBX_TRY(sbx_exclusive_scan_u32(h, present, rank, dmax + 1, nullptr));
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_sections, dim3((unsigned)((dmax + 1 + 255) / 256)), dim3(256), (const uint32_t *)present,
-                (const uint32_t *)rank, dmax + 1, (uint32_t)group_size, section);
-  } else {
-    SBX_HIP(h, hipMemsetAsync(section, 0, sizeof(uint32_t) * (size_t)(dmax + 2), h->stream));
+struct GrayOrderCall {
+  sbx_handle_t h;
+  int64_t n, nnz;
+  const I *deg;
+  const uint64_t *gkey;
+  I *inv_out;
+  int sparse_banded, dense_banded;  // 1: a "highly banded" class (gray_reorder.cc:181-190)
+  int64_t thr, dmax;                // the nnz threshold (-1: no row is sparse); the largest degree a sparse row can have
+  uint32_t gs, grid;                // distinct degrees per section: the group size, at least 1; grid of the kernels over the rows
+  int bits;                         // of a key, and `mask` with those bits set
+  uint64_t mask, *qa, *qb;          // scratch: 64-bit key buffers of n,
+  uint32_t *ia, *ib, *present, *rank, *section;  // id buffers of n, degree tables of dmax + 2
+};
+
+// `sections`: the call finds the degrees' sections (`present` zeroed for the kernel that fills it); else `section` zeroed
+template <typename I>
+int gray_order_scratch(GrayOrderCall<I> &c, bool sections) {
+  const size_t n = (size_t)c.n, nd = (size_t)c.dmax + 2;
+  SBX_TRY(sbx_salloc(c.h, n, &c.ia));
+  SBX_TRY(sbx_salloc(c.h, n, &c.ib));
+  SBX_TRY(sbx_salloc(c.h, n, &c.qa));
+  SBX_TRY(sbx_salloc(c.h, n, &c.qb));
+  SBX_TRY(sbx_salloc(c.h, nd, &c.section));
+  if (sections) SBX_TRY(sbx_salloc(c.h, nd, &c.present));
+  if (sections) SBX_TRY(sbx_salloc(c.h, nd, &c.rank));
+  SBX_HIP(c.h, hipMemsetAsync(sections ? c.present : c.section, 0, sizeof(uint32_t) * nd, c.h->stream));
+  return SBX_OK;
+}
+// present -> rank -> section; n_present != nullptr: the number of degrees present is read back on the way
+template <typename I>
+int gray_order_sections(const GrayOrderCall<I> &c, uint32_t *n_present) {
+  uint32_t *tot = nullptr;
+  if (n_present) SBX_TRY(sbx_salloc(c.h, 1, &tot));
+  SBX_TRY(sbx_exclusive_scan_u32(c.h, c.present, c.rank, c.dmax + 1, tot));
+  if (n_present) SBX_TRY(sbx_readback(c.h, n_present, tot, sizeof(uint32_t)));
+  SBX_KLAUNCH(c.h, SBX_K_GRAY, k_go_sections, dim3((unsigned)((c.dmax + 1 + 255) / 256)), dim3(256),
+              (const uint32_t *)c.present, (const uint32_t *)c.rank, c.dmax + 1, c.gs, c.section);
+  return SBX_OK;
+}
+
+// one sort of composite keys: cbits of class / section (dense_class: the dense rows'), kbits of signed key, dbits of degree
+template <typename I>
+int gray_order_one_sort(GrayOrderCall<I> &c, int cbits, int kbits, int dbits, uint32_t dense_class) {
+  sbx_handle_t h = c.h;
+  const int64_t n = c.n;
+  const bool sections = !c.sparse_banded && c.dmax > 0;  // (a "highly banded" sparse class has none)
+  SBX_TRY(gray_order_scratch(c, sections));
+  if (sections) {
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_present<I>, dim3(c.grid), dim3(256), c.deg, n, c.thr, c.present);
+    SBX_TRY(gray_order_sections(c, nullptr));
   }
   sbx_radix_pass passes[16];
   // Where the row id fits below the criteria (bench line: 39 + 22 bits) it is the key's low field: the sort moves 8-byte
   // keys without a payload, and its last pass writes inv[id] = position itself (sbx_radix_emit::pos_of) — no emit kernel
-  const int idbits = sbx_bits_for((uint64_t)(n - 1));
-  if (cbits + kbits + dbits + idbits <= 64) {
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_composite<I>, dim3(grid), dim3(256), deg, gkey, n, thr, (const uint32_t *)section,
-                sparse_banded ? 1 : 0, dense_banded ? 1 : 0, mask, dense_class, kbits, dbits, idbits, qa, (uint32_t *)nullptr);
-    SBX_LAUNCH_CHECK(h);
-    const int np = sbx_radix_plan(idbits, idbits + cbits + kbits + dbits, 0, 0, passes);
-    const sbx_radix_emit em = {nullptr, ia, nullptr, nullptr, sizeof(I) == 4 ? (unsigned *)inv_out : (unsigned *)ib,
-                               idbits < 32 ? (1u << idbits) - 1u : 0u};
-    h->rs_tied_hint = true;  // (class and degree fields of a handful of values, Gray keys shared by many rows)
-    const int rc_sort = sbx_radix_sort_emit(h, qa, qb, n, passes, np, &em);
-    h->rs_tied_hint = false;
-    SBX_TRY(rc_sort);
-    if (sizeof(I) != 4) {
-      SBX_KLAUNCH(h, SBX_K_GRAY, k_go_widen<I>, dim3(grid), dim3(256), (const uint32_t *)ib, n, inv_out);
-      SBX_LAUNCH_CHECK(h);
-    }
-    return SBX_OK;
-  }
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_composite<I>, dim3(grid), dim3(256), deg, gkey, n, thr, (const uint32_t *)section,
-              sparse_banded ? 1 : 0, dense_banded ? 1 : 0, mask, dense_class, kbits, dbits, 0, qa, ia);
+  const int fit = sbx_bits_for((uint64_t)(n - 1)), idbits = cbits + kbits + dbits + fit <= 64 ? fit : 0;  // 0: a payload
+  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_composite<I>, dim3(c.grid), dim3(256), c.deg, c.gkey, n, c.thr, (const uint32_t *)c.section,
+              c.sparse_banded, c.dense_banded, c.mask, dense_class, kbits, dbits, idbits, c.qa, idbits ? (uint32_t *)nullptr : c.ia);
   SBX_LAUNCH_CHECK(h);
-  int in_b = 0;
-  const int np = sbx_radix_plan(0, cbits + kbits + dbits, 0, 0, passes);
-  h->rs_tied_hint = true;
-  const int rc_sort = sbx_radix_sort(h, 8, 4, qa, qb, ia, ib, n, passes, np, &in_b);
-  h->rs_tied_hint = false;
-  SBX_TRY(rc_sort);
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_emit<I>, dim3(grid), dim3(256), (const uint32_t *)(in_b ? ib : ia), n, inv_out);
+  const int np = sbx_radix_plan(idbits, idbits + cbits + kbits + dbits, 0, 0, passes);
+  sbx_tied_hint_scope tied(h);  // (class and degree fields of a handful of values, Gray keys shared by many rows)
+  if (idbits) {
+    const sbx_radix_emit em = {nullptr, c.ia, nullptr, nullptr, sizeof(I) == 4 ? (unsigned *)c.inv_out : (unsigned *)c.ib,
+                               idbits < 32 ? (1u << idbits) - 1u : 0u};
+    SBX_TRY(sbx_radix_sort_emit(h, c.qa, c.qb, n, passes, np, &em));
+    if (sizeof(I) != 4)
+      SBX_KLAUNCH(h, SBX_K_GRAY, k_go_widen<I>, dim3(c.grid), dim3(256), (const uint32_t *)c.ib, n, c.inv_out);
+  } else {
+    int in_b = 0;
+    SBX_TRY(sbx_radix_sort(h, 8, 4, c.qa, c.qb, c.ia, c.ib, n, passes, np, &in_b));
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_emit<I>, dim3(c.grid), dim3(256), (const uint32_t *)(in_b ? c.ib : c.ia), n, c.inv_out);
+  }
+  SBX_LAUNCH_CHECK(h);
+  return SBX_OK;
+}
+
+// three stable sorts of (key, row id) pairs, last criterion first
+template <typename I>
+int gray_order_three_sorts(GrayOrderCall<I> &c) {
+  sbx_handle_t h = c.h;
+  const int64_t n = c.n;
+  uint32_t *ka = nullptr, *kb = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)n, &ka));
+  SBX_TRY(sbx_salloc(h, (size_t)n, &kb));
+  SBX_TRY(gray_order_scratch(c, true));
+  // 1: by degree (sparse rows; stable: ids ascending inside a degree)
+  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_degree_keys<I>, dim3(c.grid), dim3(256), c.deg, n, c.thr, ka, c.ia, c.present);
+  SBX_LAUNCH_CHECK(h);
+  uint32_t *id = c.ia, *id_tmp = c.ib;
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)c.dmax)));
+  uint32_t n_present = 0;
+  SBX_TRY(gray_order_sections(c, &n_present));  // the sections of the degrees
+  const uint32_t n_sections = c.sparse_banded ? 0u : (n_present + c.gs - 1u) / c.gs;
+  // 2: by the signed key
+  if (!(c.sparse_banded && c.dense_banded)) {
+    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_signed_keys<I>, dim3(c.grid), dim3(256), (const uint32_t *)id, c.deg, c.gkey, n, c.thr,
+                (const uint32_t *)c.section, c.sparse_banded, c.dense_banded, c.mask, c.qa);
+    SBX_LAUNCH_CHECK(h);
+    SBX_TRY(sbx_sort_pairs(h, &c.qa, &c.qb, &id, &id_tmp, n, 0, c.bits));
+  }
+  // 3: by (class, section)
+  const uint32_t dense_class = n_sections + 1u;
+  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_class_keys<I>, dim3(c.grid), dim3(256), (const uint32_t *)id, c.deg, n, c.thr,
+              (const uint32_t *)c.section, c.sparse_banded, dense_class, ka);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)dense_class)));
+  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_emit<I>, dim3(c.grid), dim3(256), (const uint32_t *)id, n, c.inv_out);
   SBX_LAUNCH_CHECK(h);
   return SBX_OK;
 }
 
 template <typename I>
-int gray_order_typed(sbx_handle_t h, int64_t n, int64_t nnz, const I *deg, const uint64_t *gkey, const int64_t *counts,
-                     int bits, int64_t thr, int group_size, I *inv_out) {
+int gray_order_typed(GrayOrderCall<I> c, const int64_t *counts, int bits, int64_t thr, int group_size) {
   // gray_reorder.cc:181-190 (the reference keeps the counters in `int`)
-  const bool sparse_banded = double((int)counts[1]) / (int)counts[0] > 0.3;
-  const bool dense_banded = double((int)counts[3]) / (int)counts[2] > 0.2;
-  if (thr < 0) thr = -1;  // no row is sparse
+  c.sparse_banded = double((int)counts[1]) / (int)counts[0] > 0.3;
+  c.dense_banded = double((int)counts[3]) / (int)counts[2] > 0.2;
+  c.thr = thr < 0 ? -1 : thr;
   // a sparse row's degree is at most the threshold (and, without duplicate columns, m; the tables cover min(threshold, nnz))
-  const int64_t dmax = thr < 0 ? 0 : (thr < nnz ? thr : nnz);
-  if (dmax > ((int64_t)1 << 28))
-    SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "sbx_gray_reorder: nnz_threshold %lld: the degree tables would need %lld entries",
-             (long long)thr, (long long)dmax);
-  {
-    // the one-sort form: do the three fields fit a word?  (at most dmax degrees are present: that many sections at most)
-    const int64_t gs = group_size > 0 ? group_size : 1;
-    const uint32_t dense_class_1 = sparse_banded ? 1u : (uint32_t)((dmax + gs - 1) / gs) + 1u;
-    const int cbits = sbx_bits_for((uint64_t)dense_class_1), dbits1 = sbx_bits_for((uint64_t)dmax);
-    const int kbits = (sparse_banded && dense_banded) ? 0 : bits;
-    if (cbits + kbits + dbits1 <= 64 && !sbx_sw().gray_three_sorts)
-      return gray_order_one_sort<I>(h, n, deg, gkey, sparse_banded, dense_banded, kbits, dbits1, cbits, dense_class_1, dmax,
-                                    thr, (int)gs, bits >= 64 ? ~0ull : ((1ull << bits) - 1ull), inv_out);
-  }
-  const unsigned grid = sbx_grid_for(n, 256, (int64_t)h->num_cus * 16);
-  uint32_t *ka = nullptr, *kb = nullptr, *ia = nullptr, *ib = nullptr, *present = nullptr, *rank = nullptr, *section = nullptr;
-  uint64_t *qa = nullptr, *qb = nullptr;
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ka));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &kb));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ia));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &ib));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &qa));
-  SBX_TRY(sbx_salloc(h, (size_t)n, &qb));
-  SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &present));
-  SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &rank));
-  SBX_TRY(sbx_salloc(h, (size_t)dmax + 2, &section));
-  SBX_HIP(h, hipMemsetAsync(present, 0, sizeof(uint32_t) * (size_t)(dmax + 2), h->stream));
-  // 1: by degree (sparse rows; stable: ids ascending inside a degree)
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_degree_keys<I>, dim3(grid), dim3(256), deg, n, thr, ka, ia, present);
-  SBX_LAUNCH_CHECK(h);
-  uint32_t *id = ia, *id_tmp = ib;
-  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)dmax)));
-  // the sections of the degrees
-  uint32_t n_present = 0, *tot = nullptr;
-  SBX_TRY(sbx_salloc(h, 1, &tot));
-  SBX_TRY(sbx_exclusive_scan_u32(h, present, rank, dmax + 1, tot));
-  SBX_TRY(sbx_readback(h, &n_present, tot, sizeof(uint32_t)));
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_sections, dim3((unsigned)((dmax + 1 + 255) / 256)), dim3(256), (const uint32_t *)present,
-              (const uint32_t *)rank, dmax + 1, (uint32_t)(group_size > 0 ? group_size : 1), section);
-  const uint32_t n_sections = sparse_banded ? 0u : (n_present + (uint32_t)(group_size > 0 ? group_size : 1) - 1u) / (uint32_t)(group_size > 0 ? group_size : 1);
-  // 2: by the signed key
-  const uint64_t mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
-  if (!(sparse_banded && dense_banded)) {
-    SBX_KLAUNCH(h, SBX_K_GRAY, k_go_signed_keys<I>, dim3(grid), dim3(256), (const uint32_t *)id, deg, gkey, n, thr,
-                (const uint32_t *)section, sparse_banded ? 1 : 0, dense_banded ? 1 : 0, mask, qa);
-    SBX_LAUNCH_CHECK(h);
-    SBX_TRY(sbx_sort_pairs(h, &qa, &qb, &id, &id_tmp, n, 0, bits));
-  }
-  // 3: by (class, section)
-  const uint32_t dense_class = n_sections + 1u;
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_class_keys<I>, dim3(grid), dim3(256), (const uint32_t *)id, deg, n, thr,
-              (const uint32_t *)section, sparse_banded ? 1 : 0, dense_class, ka);
-  SBX_LAUNCH_CHECK(h);
-  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &id, &id_tmp, n, 0, sbx_bits_for((uint64_t)dense_class)));
-  SBX_KLAUNCH(h, SBX_K_GRAY, k_go_emit<I>, dim3(grid), dim3(256), (const uint32_t *)id, n, inv_out);
-  SBX_LAUNCH_CHECK(h);
-  return SBX_OK;
+  c.dmax = thr < 0 ? 0 : (thr < c.nnz ? thr : c.nnz);
+  if (c.dmax > ((int64_t)1 << 28))
+    SBX_FAIL(c.h, SBX_ERR_UNSUPPORTED, "sbx_gray_reorder: nnz_threshold %lld: the degree tables would need %lld entries",
+             (long long)c.thr, (long long)c.dmax);
+  c.gs = (uint32_t)(group_size > 0 ? group_size : 1);
+  c.bits = bits, c.mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
+  c.grid = sbx_grid_for(c.n, 256, (int64_t)c.h->num_cus * 16);
+  // the one-sort form: do the three fields fit a word?  (at most dmax degrees are present: that many sections at most)
+  const uint32_t dense_class = c.sparse_banded ? 1u : (uint32_t)((c.dmax + c.gs - 1) / c.gs) + 1u;
+  const int cbits = sbx_bits_for((uint64_t)dense_class), dbits = sbx_bits_for((uint64_t)c.dmax);
+  const int kbits = (c.sparse_banded && c.dense_banded) ? 0 : bits;
+  if (cbits + kbits + dbits <= 64 && !sbx_sw().gray_three_sorts) return gray_order_one_sort(c, cbits, kbits, dbits, dense_class);
+  return gray_order_three_sorts(c);
 }
 
 }  // namespace
@@ -296,17 +305,14 @@ extern "C" int sbx_gray_reorder(sbx_handle_t h, sbx_index_type it, int64_t n, in
     return SBX_OK;
   }
   NestGuard guard(h);
-  int bits = resolution;
-  if (m < bits) bits = (int)m;  // gray_reorder.cc:206-208
   void *deg = nullptr;
   uint64_t *gkey = nullptr;
   SBX_TRY(sbx_arena_alloc(h, (size_t)n * (it == SBX_I64 ? 8 : 4), &deg));
   SBX_TRY(sbx_salloc(h, (size_t)n, &gkey));
   int64_t counts[4] = {0, 0, 0, 0};
   SBX_TRY(sbx_gray_row_keys(h, it, n, m, nnz, row_ptr, col, resolution, nnz_threshold, deg, gkey, counts));
+  const int bits = sbx_gray_bits(resolution, m), thr = nnz_threshold;
   if (it == SBX_I64)
-    return gray_order_typed<int64_t>(h, n, nnz, (const int64_t *)deg, gkey, counts, bits, (int64_t)nnz_threshold, group_size,
-                                     (int64_t *)inv_perm_out);
-  return gray_order_typed<int32_t>(h, n, nnz, (const int32_t *)deg, gkey, counts, bits, (int64_t)nnz_threshold, group_size,
-                                   (int32_t *)inv_perm_out);
+    return gray_order_typed<int64_t>({h, n, nnz, (const int64_t *)deg, gkey, (int64_t *)inv_perm_out}, counts, bits, thr, group_size);
+  return gray_order_typed<int32_t>({h, n, nnz, (const int32_t *)deg, gkey, (int32_t *)inv_perm_out}, counts, bits, thr, group_size);
 }

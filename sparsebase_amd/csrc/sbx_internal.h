@@ -135,6 +135,15 @@ struct sbx_stream_scope {
   sbx_stream_scope(const sbx_stream_scope &) = delete;
   sbx_stream_scope &operator=(const sbx_stream_scope &) = delete;
 };
+// A sort whose keys are heavily tied: h->rs_tied_hint is set while the guard lives and clear again on every way out of
+// its block (the only assignments to the flag besides sbx_create's).
+struct sbx_tied_hint_scope {
+  sbx_handle_t h;
+  explicit sbx_tied_hint_scope(sbx_handle_t h_) : h(h_) { h->rs_tied_hint = true; }
+  ~sbx_tied_hint_scope() { h->rs_tied_hint = false; }
+  sbx_tied_hint_scope(const sbx_tied_hint_scope &) = delete;
+  sbx_tied_hint_scope &operator=(const sbx_tied_hint_scope &) = delete;
+};
 void sbx_prof_begin(sbx_handle_t h, int kid);
 void sbx_prof_end(sbx_handle_t h);
 
@@ -255,6 +264,10 @@ struct sbx_switches {
   bool gray_three_sorts;     // SBX_GRAY_ORDER_THREE_SORTS, off; non-zero: three sorts even where one 64-bit key does
 };
 const sbx_switches &sbx_sw();
+
+// bits of a Gray key: the resolution, clamped to the number of columns (gray_reorder.cc:206-208) — the key stage and the
+// ordering stage must agree on it
+static inline int sbx_gray_bits(int resolution, int64_t m) { return m < resolution ? (int)m : resolution; }
 
 static inline int sbx_value_bytes(sbx_value_type vt) {
   switch (vt) {

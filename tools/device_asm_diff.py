@@ -25,7 +25,9 @@ def pieces(path):
         d[name] = body
         if sep:
             d['<trailer>'] = tail
-    return d, sorted(re.split(r'(?m)^(?=  - \.(?:agpr_count|args):)', meta))
+    # (the metadata's own trailer goes with no kernel: the entries may come in another order)
+    meta, sep, tail = meta.partition('amdhsa.target:')
+    return d, sorted(re.split(r'(?m)^(?=  - \.(?:agpr_count|args):)', meta)) + [sep + tail]
 
 
 bad = 0
