@@ -37,6 +37,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbsym.h"))
     hs.append(os.path.join(ROOT, "include", "sbmv.h"))
     hs.append(os.path.join(ROOT, "include", "sbmm.h"))
+    hs.append(os.path.join(ROOT, "include", "sbdd.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h and include/sbmm.h
+include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h, include/sbmm.h and include/sbdd.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -202,6 +202,12 @@ MM_PROTOTYPES = {
     "sbmm_csr_spmm": ([_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
 }
 
+# every symbol include/sbdd.h declares (tests/test_dd_abi.py checks header <-> library <-> this table): the sampled
+# dense-dense product on a CSR pattern, prefix `sbdd_`
+DD_PROTOTYPES = {
+    "sbdd_csr_sddmm": ([_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp], _int),
+}
+
 _lib = None
 
 
@@ -217,7 +223,8 @@ def load():
                                            list(STATS_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) +
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
                                            list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items()) +
-                                           list(MV_PROTOTYPES.items()) + list(MM_PROTOTYPES.items())):
+                                           list(MV_PROTOTYPES.items()) + list(MM_PROTOTYPES.items()) +
+                                           list(DD_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

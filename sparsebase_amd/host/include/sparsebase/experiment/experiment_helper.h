@@ -1,4 +1,4 @@
-// Loaders, preprocess functions and the SpMV and SpMM kernel functions for experiment::ConcreteExperiment (reference:
+// Loaders, preprocess functions and the SpMV, SpMM and SDDMM kernel functions for experiment::ConcreteExperiment (reference:
 // experiment/experiment_helper.h:21-124 for LoadFormat ... Reorder; the rest is this project's own).
 //
 //   LoadFormat / LoadCSR / LoadCOO / LoadCSC   file_names[0] through ReaderType into data["format"]
@@ -7,6 +7,7 @@
 //                                              no kernel call of the canonical pipeline pays a trip over PCIe
 //   SpMV<I, N, V, F>                           the KernelFunction: y = A x on the device (kernels/spmv.h)
 //   SpMM<I, N, V, F>                           the KernelFunction: Y = A X for k columns on the device (kernels/spmm.h)
+//   SDDMM<I, N, V, F>                          the KernelFunction: out = vals (.) (U V^T) on A's pattern (kernels/sddmm.h)
 //
 // As in the reference, the ContextType of ReorderCSR and Reorder is default-constructed: that is CPUContext, whose
 // formats the host layer stages through the device as it does everywhere.
@@ -23,6 +24,7 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/kernels/sddmm.h"
 #include "sparsebase/kernels/spmm.h"
 #include "sparsebase/kernels/spmv.h"
 
@@ -188,6 +190,49 @@ std::any SpMM(DataMap &data, std::any &fparams, std::any &pparams, std::any &kpa
     throw;
   }
   return y;
+}
+
+// The kernel parameter of SDDMM: the number of columns of U and V, U (n * k values row-major, an Array<FloatType> or an
+// HIPArray<FloatType>) and, optionally, the values (the same two types; empty: the matrix's own values where ValueType is
+// FloatType, else a pattern).
+struct SDDMMParams {
+  size_t k = 1;
+  std::any u;
+  std::any vals;
+};
+
+// The SDDMM KernelFunction, with SpMM's contract: data["processed_format"] is a CSR or an HIPCSR of <IDType, NNZType,
+// ValueType>; fparams holds V, m * k values row-major, as an Array<FloatType> or an HIPArray<FloatType>; kparams holds an
+// SDDMMParams.  The result is a host FloatType* of nnz values from new[], owned by the caller, returned after the device
+// has finished.  Host data is staged on every call, inside the harness's timing; device-resident data pays the download of
+// the result alone.
+template <typename IDType, typename NNZType, typename ValueType, typename FloatType>
+std::any SDDMM(DataMap &data, std::any &fparams, std::any &pparams, std::any &kparams) {
+  typedef reorder::detail::DeviceCsrView<IDType, NNZType, ValueType> View;
+  auto *params = std::any_cast<SDDMMParams>(&kparams);
+  if (!params) throw utils::TypeException("experiment::SDDMM: the kernel's parameter must be an SDDMMParams");
+  format::Format *A = data.at("processed_format");
+  const bool resident = A->template IsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>();
+  const bool has_vals = params->vals.has_value();
+  const bool own_vals = !has_vals && std::is_same_v<ValueType, FloatType>;
+  View v = resident ? View::Borrow(A->template AsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>())
+                    : View::Stage(A->template AsAbsolute<format::CSR<IDType, NNZType, ValueType>>(), own_vals);
+  utils::detail::CsrViewGuard<IDType, NNZType, ValueType> guard{v};
+  auto x = detail::OperandOf<FloatType>(fparams, *v.dev, "experiment::SDDMM: ", "V (the file's parameter)");
+  auto u = detail::OperandOf<FloatType>(params->u, *v.dev, "experiment::SDDMM: ", "U (the kernel's parameter)");
+  kernels::detail::DeviceVector<FloatType> vals;
+  if (has_vals) vals = detail::OperandOf<FloatType>(params->vals, *v.dev, "experiment::SDDMM: ", "the values (the kernel's parameter)");
+  const size_t count = (size_t)v.nnz;
+  hip::Staged<FloatType> d_out(*v.dev, count ? count : 1);
+  kernels::detail::SampleBlock(v, u, x, params->k, has_vals ? &vals : nullptr, d_out.get());
+  FloatType *out = new FloatType[count ? count : 1];
+  try {
+    d_out.ToHost(out);  // (a blocking copy behind the kernel on the handle's stream: the synchronise)
+  } catch (...) {
+    delete[] out;
+    throw;
+  }
+  return out;
 }
 
 }  // namespace sparsebase::experiment

@@ -1,4 +1,5 @@
-"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h, sbmm.h).
+"""Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h, sbmm.h,
+sbdd.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -520,6 +521,38 @@ def csr_spmm(row_ptr, col, X, val=None, m=None, out=None):
     hd.check(hd.lib.sbmm_csr_spmm(hd.h, _it(row_ptr, col), _vt(X), n, m, col.numel(), k, _p(row_ptr), _p(col), _p(val),
                                   _p(X), _ld(X), _p(y), _ld(y)))
     return y
+
+
+# ----------------------------------------------------------------------------- out = val (.) (U V^T) (include/sbdd.h)
+def csr_sddmm(row_ptr, col, U, V, val=None, out=None):
+    """The sampled dense-dense product on a CSR pattern: out[p] = val[p] * (U[row(p), :] . V[col[p], :]) for every stored
+    entry p, a 1-D device tensor of col.numel() values of U's dtype (float32, float64, int32 or int64; integers wrap).  U
+    is (n, k) and V is (m, k), both 2-D with stride(1) == 1 (a column slice of a wider tensor is fine: its stride(0) is the
+    leading dimension); val=None is a pattern matrix (every stored value 1, out[p] the dot itself).  Deterministic,
+    asynchronous and independent of where an entry lies; an entry whose column lies outside [0, m) gets +0.  See
+    sbdd_csr_sddmm in include/sbdd.h."""
+    dev = _check_dev(row_ptr, col, val, out)
+    for t, what in ((U, "U"), (V, "V")):
+        if not (t.is_cuda and t.dim() == 2 and t.numel() == 0):  # (the strides of a tensor without elements say nothing)
+            _check_rows(t, what)
+    if U.device != dev or V.device != dev:
+        raise ValueError("all tensors must live on the same device")
+    n, nnz, k = row_ptr.numel() - 1, col.numel(), int(U.shape[1])
+    if int(U.shape[0]) != n:
+        raise ValueError(f"U holds {U.shape[0]} rows, the matrix has {n}")
+    if int(V.shape[1]) != k:
+        raise ValueError(f"U has {k} columns, V has {V.shape[1]}")
+    if V.dtype != U.dtype or U.dtype not in _VT:
+        raise ValueError("U and V must have the same dtype: float32, float64, int32 or int64")
+    if val is not None and (val.dtype != U.dtype or val.dim() != 1 or val.numel() != nnz):
+        raise ValueError("val must be 1-D with the dtype of U and one value per stored entry")
+    o = torch.empty(nnz, dtype=U.dtype, device=U.device) if out is None else out
+    if o.dtype != U.dtype or o.dim() != 1 or o.numel() != nnz:
+        raise ValueError("out must be 1-D with the dtype of U and one value per stored entry")
+    hd = handle_for(dev)
+    hd.check(hd.lib.sbdd_csr_sddmm(hd.h, _it(row_ptr, col), _vt(U), n, int(V.shape[0]), nnz, k, _p(row_ptr), _p(col), _p(val),
+                                   _p(U), _ld(U), _p(V), _ld(V), _p(o)))
+    return o
 
 
 def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
