@@ -38,6 +38,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbmv.h"))
     hs.append(os.path.join(ROOT, "include", "sbmm.h"))
     hs.append(os.path.join(ROOT, "include", "sbdd.h"))
+    hs.append(os.path.join(ROOT, "include", "sbsm.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h, include/sbmm.h and include/sbdd.h
+include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h, include/sbmm.h, include/sbdd.h and include/sbsm.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -208,6 +208,13 @@ DD_PROTOTYPES = {
     "sbdd_csr_sddmm": ([_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp], _int),
 }
 
+# every symbol include/sbsm.h declares (tests/test_sm_abi.py checks header <-> library <-> this table): the row softmax
+# over a CSR's stored values and its backward, prefix `sbsm_`
+SM_PROTOTYPES = {
+    "sbsm_csr_row_softmax": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp], _int),
+    "sbsm_csr_row_softmax_backward": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+}
+
 _lib = None
 
 
@@ -224,7 +231,7 @@ def load():
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
                                            list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items()) +
                                            list(MV_PROTOTYPES.items()) + list(MM_PROTOTYPES.items()) +
-                                           list(DD_PROTOTYPES.items())):
+                                           list(DD_PROTOTYPES.items()) + list(SM_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

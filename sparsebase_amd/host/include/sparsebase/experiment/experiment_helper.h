@@ -1,4 +1,4 @@
-// Loaders, preprocess functions and the SpMV, SpMM and SDDMM kernel functions for experiment::ConcreteExperiment (reference:
+// Loaders, preprocess functions and the SpMV, SpMM, SDDMM and RowSoftmax kernel functions for experiment::ConcreteExperiment (reference:
 // experiment/experiment_helper.h:21-124 for LoadFormat ... Reorder; the rest is this project's own).
 //
 //   LoadFormat / LoadCSR / LoadCOO / LoadCSC   file_names[0] through ReaderType into data["format"]
@@ -8,6 +8,7 @@
 //   SpMV<I, N, V, F>                           the KernelFunction: y = A x on the device (kernels/spmv.h)
 //   SpMM<I, N, V, F>                           the KernelFunction: Y = A X for k columns on the device (kernels/spmm.h)
 //   SDDMM<I, N, V, F>                          the KernelFunction: out = vals (.) (U V^T) on A's pattern (kernels/sddmm.h)
+//   RowSoftmax<I, N, V, F>                     the KernelFunction: the softmax of every row's values (kernels/row_softmax.h)
 //
 // As in the reference, the ContextType of ReorderCSR and Reorder is default-constructed: that is CPUContext, whose
 // formats the host layer stages through the device as it does everywhere.
@@ -24,6 +25,7 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/kernels/row_softmax.h"
 #include "sparsebase/kernels/sddmm.h"
 #include "sparsebase/kernels/spmm.h"
 #include "sparsebase/kernels/spmv.h"
@@ -228,6 +230,37 @@ std::any SDDMM(DataMap &data, std::any &fparams, std::any &pparams, std::any &kp
   FloatType *out = new FloatType[count ? count : 1];
   try {
     d_out.ToHost(out);  // (a blocking copy behind the kernel on the handle's stream: the synchronise)
+  } catch (...) {
+    delete[] out;
+    throw;
+  }
+  return out;
+}
+
+// The RowSoftmax KernelFunction, with SDDMM's contract: data["processed_format"] is a CSR or an HIPCSR of <IDType, NNZType,
+// ValueType>; kparams holds the values, one per stored entry, as an Array<FloatType> or an HIPArray<FloatType>, or nothing
+// (then the matrix's own values where ValueType is FloatType, else a pattern: 1 / the entries of the row); fparams is not
+// read.  The result is a host FloatType* of nnz values from new[], owned by the caller, returned after the device has
+// finished.  Host data is staged on every call, inside the harness's timing; device-resident data pays the download of the
+// result alone.
+template <typename IDType, typename NNZType, typename ValueType, typename FloatType>
+std::any RowSoftmax(DataMap &data, std::any &fparams, std::any &pparams, std::any &kparams) {
+  typedef reorder::detail::DeviceCsrView<IDType, NNZType, ValueType> View;
+  format::Format *A = data.at("processed_format");
+  const bool resident = A->template IsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>();
+  const bool has_vals = kparams.has_value();
+  const bool own_vals = !has_vals && std::is_same_v<ValueType, FloatType>;
+  View v = resident ? View::Borrow(A->template AsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>())
+                    : View::Stage(A->template AsAbsolute<format::CSR<IDType, NNZType, ValueType>>(), own_vals);
+  utils::detail::CsrViewGuard<IDType, NNZType, ValueType> guard{v};
+  kernels::detail::DeviceVector<FloatType> vals;
+  if (has_vals) vals = detail::OperandOf<FloatType>(kparams, *v.dev, "experiment::RowSoftmax: ", "the values (the kernel's parameter)");
+  const size_t count = (size_t)v.nnz;
+  hip::Staged<FloatType> d_out(*v.dev, count ? count : 1);
+  kernels::detail::NormalizeRows(v, has_vals ? &vals : nullptr, d_out.get());
+  FloatType *out = new FloatType[count ? count : 1];
+  try {
+    d_out.ToHost(out);  // (a blocking copy behind the kernels on the handle's stream: the synchronise)
   } catch (...) {
     delete[] out;
     throw;

@@ -37,6 +37,7 @@
 #include "sparsebase/format/csc.h"
 #include "sparsebase/format/csr.h"
 #include "sparsebase/format/hip_formats.h"
+#include "sparsebase/kernels/row_softmax.h"
 #include "sparsebase/kernels/sddmm.h"
 #include "sparsebase/kernels/spmm.h"
 #include "sparsebase/kernels/spmv.h"

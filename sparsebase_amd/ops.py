@@ -1,5 +1,5 @@
 """Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h, sbmm.h,
-sbdd.h).
+sbdd.h, sbsm.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -553,6 +553,80 @@ def csr_sddmm(row_ptr, col, U, V, val=None, out=None):
     hd.check(hd.lib.sbdd_csr_sddmm(hd.h, _it(row_ptr, col), _vt(U), n, int(V.shape[0]), nnz, k, _p(row_ptr), _p(col), _p(val),
                                    _p(U), _ld(U), _p(V), _ld(V), _p(o)))
     return o
+
+
+# ----------------------------------------------------------------------------- row softmax (include/sbsm.h)
+_FLOATS = (torch.float32,)  # (float64 is not built yet: include/sbsm.h)
+
+
+def _check_entries(t, what, dtype, nnz):
+    if t.dtype != dtype or t.dim() != 1 or t.numel() != nnz:
+        raise ValueError(f"{what} must be 1-D with dtype {dtype} and one value per stored entry ({nnz})")
+
+
+def csr_row_softmax(row_ptr, val, out=None, dtype=None, nnz=None):
+    """The softmax over the stored values of every row of a CSR matrix: out[p] = exp(val[p] - max_i) / sum_i, a 1-D device
+    tensor of one float32 value per stored entry.  -inf masks an entry (+0; a row of -inf alone is +0
+    everywhere); a row with a NaN or a +inf is NaN throughout.  val=None is a pattern (every stored value equal: out[p] =
+    1 / len_i) and needs dtype= and nnz=.  `out` may be `val` itself.  Deterministic and asynchronous.  See
+    sbsm_csr_row_softmax in include/sbsm.h."""
+    dev = _check_dev(row_ptr, val, out)
+    if row_ptr.dim() != 1 or row_ptr.numel() < 1:
+        raise ValueError("row_ptr must be 1-D with n + 1 offsets")
+    if val is None:
+        if dtype is None or nnz is None:
+            raise ValueError("val=None (a pattern) needs dtype= and nnz=")
+        nnz = int(nnz)
+    else:
+        if (dtype is not None and dtype != val.dtype) or (nnz is not None and int(nnz) != val.numel()):
+            raise ValueError("dtype= and nnz= disagree with val")
+        dtype, nnz = val.dtype, val.numel()
+        _check_entries(val, "val", dtype, nnz)
+    if dtype not in _FLOATS:
+        raise ValueError("the values must be float32")
+    o = torch.empty(nnz, dtype=dtype, device=dev) if out is None else out
+    _check_entries(o, "out", dtype, nnz)
+    hd = handle_for(dev)
+    hd.check(hd.lib.sbsm_csr_row_softmax(hd.h, _it(row_ptr), _VT[dtype], row_ptr.numel() - 1, nnz, _p(row_ptr), _p(val), _p(o)))
+    return o
+
+
+def csr_row_softmax_backward(row_ptr, s, g, out=None):
+    """The backward of csr_row_softmax: dz[p] = s[p] * (g[p] - sum over the row of s[q] g[q]), with s the forward's output
+    and g the gradient with respect to it.  `out` may be `g` itself.  Deterministic and asynchronous.  See
+    sbsm_csr_row_softmax_backward in include/sbsm.h."""
+    dev = _check_dev(row_ptr, s, g, out)
+    if row_ptr.dim() != 1 or row_ptr.numel() < 1:
+        raise ValueError("row_ptr must be 1-D with n + 1 offsets")
+    if s.dtype not in _FLOATS:
+        raise ValueError("the values must be float32")
+    nnz = s.numel()
+    _check_entries(s, "s", s.dtype, nnz)
+    _check_entries(g, "g", s.dtype, nnz)
+    o = torch.empty_like(s) if out is None else out
+    _check_entries(o, "out", s.dtype, nnz)
+    hd = handle_for(dev)
+    hd.check(hd.lib.sbsm_csr_row_softmax_backward(hd.h, _it(row_ptr), _VT[s.dtype], row_ptr.numel() - 1, nnz, _p(row_ptr),
+                                                  _p(s), _p(g), _p(o)))
+    return o
+
+
+class _RowSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, row_ptr, val):
+        s = csr_row_softmax(row_ptr, val.detach().contiguous())
+        ctx.save_for_backward(row_ptr, s)
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        row_ptr, s = ctx.saved_tensors
+        return None, csr_row_softmax_backward(row_ptr, s, g.contiguous())
+
+
+def csr_row_softmax_autograd(row_ptr, val):
+    """csr_row_softmax as a differentiable function of val: the backward is one call of csr_row_softmax_backward."""
+    return _RowSoftmax.apply(row_ptr, val)
 
 
 def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
