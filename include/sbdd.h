@@ -54,7 +54,7 @@
  * second checker.
  *
  * Out of scope: out = alpha val (U V^T) + beta out and accumulation into out, column-major U or V, 2-byte value types,
- * CSC and COO patterns, sharded matrices.
+ * CSC and COO patterns, sharded matrices.  (The gradient with respect to V is a product with the transpose: sbmt.h.)
  */
 #ifndef SBDD_H_
 #define SBDD_H_

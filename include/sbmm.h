@@ -38,8 +38,8 @@
  * unspecified, but no access leaves the arrays.  A caller that wants a refusal instead calls sbmv_csr_check (sbmv.h)
  * once: there is no second checker.
  *
- * Out of scope: Y = alpha A X + beta Y, the transposed product, column-major X or Y, CSC and COO inputs, 2-byte value
- * types, sharded matrices.
+ * Out of scope: Y = alpha A X + beta Y, the transposed product (a header of its own: sbmt.h), column-major X or Y, CSC and
+ * COO inputs, 2-byte value types, sharded matrices.
  */
 #ifndef SBMM_H_
 #define SBMM_H_

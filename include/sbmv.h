@@ -34,8 +34,8 @@
  * non-decreasing sequence from 0 to nnz gives is otherwise unspecified, but no access leaves the arrays.  A caller that
  * wants a refusal instead calls sbmv_csr_check once.
  *
- * Out of scope: y = alpha A x + beta y, the transposed product, several right-hand sides, CSC and COO inputs, sharded
- * matrices.
+ * Out of scope: y = alpha A x + beta y, the transposed product (sbmt.h has it for k columns, k = 1 among them), several
+ * right-hand sides, CSC and COO inputs, sharded matrices.
  */
 #ifndef SBMV_H_
 #define SBMV_H_

@@ -39,6 +39,7 @@ def _headers_mtime():
     hs.append(os.path.join(ROOT, "include", "sbmm.h"))
     hs.append(os.path.join(ROOT, "include", "sbdd.h"))
     hs.append(os.path.join(ROOT, "include", "sbsm.h"))
+    hs.append(os.path.join(ROOT, "include", "sbmt.h"))
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/sbx.h, include/sbx_text.h, include/sbx_stats.h, include/sbio.h, include/sbgr.h,
-include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h, include/sbmm.h, include/sbdd.h and include/sbsm.h
+include/sbhg.h, include/sbfx.h, include/sbsym.h, include/sbmv.h, include/sbmm.h, include/sbdd.h, include/sbsm.h and include/sbmt.h
 (sparsebase_amd/lib/libsbx.so).
 
 There is deliberately NO fallback: if the library is missing or no GPU is
@@ -215,6 +215,13 @@ SM_PROTOTYPES = {
     "sbsm_csr_row_softmax_backward": ([_H, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp], _int),
 }
 
+# every symbol include/sbmt.h declares (tests/test_mt_abi.py checks header <-> library <-> this table): the plan of the
+# transpose and the transposed product from it, prefix `sbmt_`
+MT_PROTOTYPES = {
+    "sbmt_csr_transpose_plan": ([_H, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp], _int),
+    "sbmt_csr_spmm_t": ([_H, _int, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
+}
+
 _lib = None
 
 
@@ -231,7 +238,8 @@ def load():
                                            list(GRAPH_PROTOTYPES.items()) + list(HYPERGRAPH_PROTOTYPES.items()) +
                                            list(EXTRACT_PROTOTYPES.items()) + list(SYM_PROTOTYPES.items()) +
                                            list(MV_PROTOTYPES.items()) + list(MM_PROTOTYPES.items()) +
-                                           list(DD_PROTOTYPES.items()) + list(SM_PROTOTYPES.items())):
+                                           list(DD_PROTOTYPES.items()) + list(SM_PROTOTYPES.items()) +
+                                           list(MT_PROTOTYPES.items())):
             fn = getattr(lib, name)  # AttributeError here == header/library drift: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -16,6 +16,9 @@
 //   CSR->COO  each 2048-nnz tile finds its row span with a wave-wide 64-ary
 //             search, scatters row heads into LDS, max-scans them and streams
 //             row ids + col/val copies out.
+#include <type_traits>
+
+#include "sbmt.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
 
@@ -1053,4 +1056,89 @@ extern "C" int sbx_csr_to_csc(sbx_handle_t h, sbx_index_type it, sbx_value_type 
   }
   return coo_to_csc_core(h, vt, n, m, nnz, rows, (const int32_t *)col, (const char *)val, (int32_t *)col_ptr_out,
                          (int32_t *)row_out, (char *)val_out, /*rows_ascend=*/true);
+}
+
+// ---------------------------------------------------------------- include/sbmt.h: the plan of the transposed product
+// A15 without values and with the source position of every entry kept: the stable sort of (column, position) records
+// that coo_to_csc_core runs for 8-byte values and coo_to_csc_core64 always, the rows gathered through the sorted
+// positions, col_ptr from the sorted columns.  The positions are the plan's perm: nothing is gathered through them here
+// but the rows, and the values never enter.
+namespace {
+
+template <typename I, typename N>
+__global__ __launch_bounds__(CV_THREADS) void k_plan_emit(const uint32_t *__restrict__ idx, const I *__restrict__ rows,
+                                                          I *__restrict__ row_out, N *__restrict__ perm_out, int64_t nnz) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < nnz; i += stride) {
+    const uint32_t j = idx[i];  // (a permutation of 0 ... nnz - 1: the sort moves the records, it makes none)
+    row_out[i] = rows[j];
+    perm_out[i] = (N)j;
+  }
+}
+
+template <typename I, typename N>
+int transpose_plan_typed(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t m, int64_t nnz, const void *row_ptr,
+                         const void *col, void *col_ptr_out, void *row_out, void *perm_out) {
+  using K = typename std::conditional<sizeof(I) == 4, uint32_t, uint64_t>::type;
+  SBX_TRY(sbx_arena_begin(h));
+  NestGuard guard(h);
+  if (nnz == 0) return fill_index<N>(h, (N *)col_ptr_out, 0, m + 1);
+  const unsigned grid = sbx_grid_for(nnz, CV_THREADS, 8192);
+  // the columns index col_ptr_out behind the sort, and only their low bits are sorted by: one outside [0, m) is refused
+  int *outside = nullptr;
+  SBX_TRY(sbx_salloc(h, 1, &outside));
+  SBX_HIP(h, hipMemsetAsync(outside, 0, sizeof(int), h->stream));
+  SBX_KLAUNCH(h, SBX_K_CHECK, k_any_outside<I>, dim3(grid), dim3(CV_THREADS), (const I *)col, nnz, m, outside);
+  SBX_LAUNCH_CHECK(h);
+  int f = 0;
+  SBX_TRY(sbx_readback(h, &f, outside, sizeof(int)));
+  if (f) SBX_FAIL(h, SBX_ERR_BAD_ARG, "sbmt_csr_transpose_plan: a column lies outside [0, m)");
+  I *rows = nullptr;
+  K *ka = nullptr, *kb = nullptr;
+  uint32_t *ia = nullptr, *ib = nullptr;
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &rows));
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &ka));
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &kb));
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &ia));
+  SBX_TRY(sbx_salloc(h, (size_t)nnz, &ib));
+  SBX_TRY(sbx_csr_to_coo(h, it, SBX_V_NONE, n, m, nnz, row_ptr, nullptr, nullptr, rows, nullptr, nullptr, SBX_FLAG_MOVE));
+  if constexpr (sizeof(I) == 4)
+    SBX_KLAUNCH(h, SBX_K_CSC, k_csc_keys, dim3(grid), dim3(CV_THREADS), (const int32_t *)col, ka, ia, nnz);
+  else
+    SBX_KLAUNCH(h, SBX_K_CSC, k_csc_keys64, dim3(grid), dim3(CV_THREADS), (const int64_t *)col, ka, ia, nnz);
+  SBX_LAUNCH_CHECK(h);
+  SBX_TRY(sbx_sort_pairs(h, &ka, &kb, &ia, &ib, nnz, 0, sbx_bits_for(m > 0 ? (uint64_t)(m - 1) : 0)));
+  SBX_KLAUNCH(h, SBX_K_CSC, (k_plan_emit<I, N>), dim3(grid), dim3(CV_THREADS), (const uint32_t *)ia, (const I *)rows,
+              (I *)row_out, (N *)perm_out, nnz);
+  SBX_LAUNCH_CHECK(h);
+  SBX_PROF_BYTES(h, SBX_K_CSC, nnz * (int64_t)(2 * sizeof(K) + 8 + 3 * sizeof(I) + sizeof(N)));
+  // col_ptr = the row-pointer construction over the sorted columns, which are in range and in order
+  return sbx_coo_to_csr(h, it, SBX_V_NONE, m, n, nnz, ka, nullptr, nullptr, col_ptr_out, nullptr, nullptr,
+                        SBX_FLAG_MOVE | SBX_FLAG_ROWS_SORTED);
+}
+
+}  // namespace
+
+extern "C" int sbmt_csr_transpose_plan(sbx_handle_t h, sbx_index_type it, int64_t n, int64_t m, int64_t nnz,
+                                       const void *row_ptr, const void *col, void *col_ptr_out, void *row_out,
+                                       void *perm_out) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, n >= 0, "n is negative");
+  SBX_REQUIRE(h, m >= 0, "m is negative");
+  SBX_REQUIRE(h, nnz >= 0, "nnz is negative");
+  SBX_REQUIRE(h, row_ptr != nullptr, "row_ptr is NULL");
+  SBX_REQUIRE(h, col != nullptr || nnz == 0, "col is NULL");
+  SBX_REQUIRE(h, col_ptr_out != nullptr, "col_ptr_out is NULL");
+  SBX_REQUIRE(h, row_out != nullptr || nnz == 0, "row_out is NULL");
+  SBX_REQUIRE(h, perm_out != nullptr || nnz == 0, "perm_out is NULL");
+  SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64 || it == SBX_I32_N64, "unknown index type");
+  if (nnz >= ((int64_t)1 << 31)) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: nnz = %lld >= 2^31", __func__, (long long)nnz);
+  if (n >= ((int64_t)1 << 31) - 1) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: n = %lld >= 2^31 - 1", __func__, (long long)n);
+  if (m >= ((int64_t)1 << 31) - 1) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: m = %lld >= 2^31 - 1", __func__, (long long)m);
+  if (it == SBX_I32)
+    return transpose_plan_typed<int32_t, int32_t>(h, it, n, m, nnz, row_ptr, col, col_ptr_out, row_out, perm_out);
+  if (it == SBX_I32_N64)
+    return transpose_plan_typed<int32_t, int64_t>(h, it, n, m, nnz, row_ptr, col, col_ptr_out, row_out, perm_out);
+  return transpose_plan_typed<int64_t, int64_t>(h, it, n, m, nnz, row_ptr, col, col_ptr_out, row_out, perm_out);
 }

@@ -477,7 +477,7 @@ const char *const sbx_kernel_names[SBX_K_COUNT] = {
     "permute_long",  "permute_block", "permute_prep", "bfs_expand",    "bfs_heavy",  "bfs_bottom_up", "bfs_small_levels",  "level_order", "cc",
     "rcm_small",     "rcm_misc",     "gray",          "degree",     "check",       "csc",  "feature", "mtx", "misc",
     "text_format",   "text_long",    "text_write",    "text_check",   "spmv",         "spmm",         "sddmm",
-    "softmax"};
+    "softmax",       "spmm_t"};
 
 static hipEvent_t prof_event(sbx_handle_t h) {
   if (!h->prof_pool.empty()) {

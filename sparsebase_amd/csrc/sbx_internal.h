@@ -47,6 +47,7 @@ enum sbx_kernel_id {
   SBX_K_SPMM,
   SBX_K_SDDMM,
   SBX_K_SOFTMAX,
+  SBX_K_SPMM_T,
   SBX_K_COUNT
 };
 extern const char *const sbx_kernel_names[SBX_K_COUNT];

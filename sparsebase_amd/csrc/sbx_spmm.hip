@@ -29,6 +29,7 @@
 #include <cstddef>
 
 #include "sbmm.h"
+#include "sbmt.h"
 #include "sbmv.h"
 #include "sbx_device.h"
 #include "sbx_internal.h"
@@ -91,9 +92,14 @@ __global__ __launch_bounds__(MM) void k_spmm_zero(V *__restrict__ y, int64_t ldy
   y[r * ldy + (i - r * k)] = (V)0;
 }
 
-template <typename I, typename N, typename V, int VEC, bool WIDE>
+// PERM (the transposed product of sbmt.h, where rp / col are the plan's col_ptr / row): entry p's value is val[perm[p]].
+// A lane loads its positions of perm as it loads its columns and issues all its gathers from val before the first is
+// used; a position outside [0, nnz) is never loaded through and its entry contributes nothing, as a column outside
+// [0, m) does.  Nothing else differs: the sums and their order are those of PERM == false on the gathered values.
+template <typename I, typename N, typename V, int VEC, bool WIDE, bool PERM>
 __global__ __launch_bounds__(64) void k_spmm_span(const N *__restrict__ rp, const I *__restrict__ col,
-                                                  const V *__restrict__ val, const V *__restrict__ x, int64_t ldx, int64_t m,
+                                                  const N *__restrict__ perm, const V *__restrict__ val,
+                                                  const V *__restrict__ x, int64_t ldx, int64_t m,
                                                   int64_t nnz, int64_t k, int G, bool col_vec, bool val_vec,
                                                   const int64_t *__restrict__ first,
                                                   V *__restrict__ y, int64_t ldy, int64_t *__restrict__ trow,
@@ -132,14 +138,35 @@ __global__ __launch_bounds__(64) void k_spmm_span(const N *__restrict__ rp, cons
     I c[E];
     V v[E];
     int64_t r[E];
+    bool pok[E];  // (PERM: the entry's position in val lies inside the array)
+#pragma unroll
+    for (int e = 0; e < E; e++) pok[e] = true;
     if constexpr (WIDE) {
       const int64_t pc = p0 < u1 ? p0 : u1 - 1;
       c[0] = col[pc];
-      v[0] = val ? val[pc] : (V)1;
+      if constexpr (PERM) {
+        const int64_t pp = (int64_t)perm[pc];
+        pok[0] = p0 < u1 && (uint64_t)pp < (uint64_t)nnz;
+        v[0] = (V)0;
+        if (pok[0]) v[0] = val[pp];
+      } else {
+        v[0] = val ? val[pc] : (V)1;
+      }
       r[0] = r0 == r1 ? r0 : sbx_row_of(rp, pc, r0, r1);
     } else {
       sbx_load_items8(col, p0, u1, col_vec, c);
-      if (val) {
+      if constexpr (PERM) {
+        N pm[E];
+        sbx_load_items8(perm, p0, u1, val_vec, pm);  // (val_vec: perm's alignment here)
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+          pok[e] = p0 + e < u1 && (uint64_t)(int64_t)pm[e] < (uint64_t)nnz;
+          v[e] = (V)0;
+        }
+#pragma unroll
+        for (int e = 0; e < E; e++)  // the lane's gathers, all in flight before the first value is used
+          if (pok[e]) v[e] = val[(int64_t)pm[e]];
+      } else if (val) {
         sbx_load_values8(val, p0, u1, val_vec, v);
       } else {
 #pragma unroll
@@ -160,7 +187,7 @@ __global__ __launch_bounds__(64) void k_spmm_span(const N *__restrict__ rp, cons
     }
 #pragma unroll
     for (int e = 0; e < E; e++)
-      if (!(live && p0 + e < u1 && (uint64_t)(int64_t)c[e] < (uint64_t)m)) c[e] = (I)-1;
+      if (!(live && p0 + e < u1 && pok[e] && (uint64_t)(int64_t)c[e] < (uint64_t)m)) c[e] = (I)-1;
 
     // the batch's entries in order: lane by lane, and a lane's E entries in turn; MM_INFLIGHT rows of X in flight
     for (int lp = 0; lp < LP; lp += WIDE ? MM_INFLIGHT : 1) {
@@ -264,18 +291,20 @@ __global__ __launch_bounds__(MM) void k_spmm_carry(const int64_t *__restrict__ t
   y[r * ldy + j] = s + y[r * ldy + j];
 }
 
+// perm != nullptr (with val): the transposed product of sbmt.h on the plan's arrays, profiled as its own kernel group
 template <typename I, typename N, typename V>
 static int mm_spmm(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, int64_t k, const void *row_ptr, const void *col,
-                   const void *val, const void *x, int64_t ldx, void *y, int64_t ldy) {
+                   const void *val, const void *x, int64_t ldx, void *y, int64_t ldy, const void *perm = nullptr,
+                   int kid = SBX_K_SPMM) {
   SBX_HIP(h, hipSetDevice(h->device));
   if (ldy == k) {
     SBX_HIP(h, hipMemsetAsync(y, 0, (size_t)n * (size_t)k * sizeof(V), h->stream));
   } else {
-    SBX_KLAUNCH(h, SBX_K_SPMM, (k_spmm_zero<V>), dim3((unsigned)((n * k + MM - 1) / MM)), dim3(MM), (V *)y, ldy, k, n * k);
+    SBX_KLAUNCH(h, kid, (k_spmm_zero<V>), dim3((unsigned)((n * k + MM - 1) / MM)), dim3(MM), (V *)y, ldy, k, n * k);
   }
   if (nnz == 0) {  // (the same declaration as below with nnz = 0: the zero fill is the whole product)
     SBX_LAUNCH_CHECK(h);
-    SBX_PROF_BYTES(h, SBX_K_SPMM, n * (int64_t)sizeof(N) + (m + n) * k * (int64_t)sizeof(V));
+    SBX_PROF_BYTES(h, kid, n * (int64_t)sizeof(N) + (m + n) * k * (int64_t)sizeof(V));
     return SBX_OK;
   }
   SBX_TRY(sbx_arena_begin(h));
@@ -285,7 +314,7 @@ static int mm_spmm(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, int64_t k,
   SBX_TRY(sbx_salloc(h, (size_t)spans + 1, &first));
   SBX_TRY(sbx_salloc(h, (size_t)spans, &trow));
   SBX_TRY(sbx_salloc(h, (size_t)spans * (size_t)k, &tsum));
-  SBX_KLAUNCH(h, SBX_K_SPMM, (k_tile_first_rows<N, MM_SPAN, MM>), dim3((unsigned)((spans + 1 + MM - 1) / MM)), dim3(MM),
+  SBX_KLAUNCH(h, kid, (k_tile_first_rows<N, MM_SPAN, MM>), dim3((unsigned)((spans + 1 + MM - 1) / MM)), dim3(MM),
               (const N *)row_ptr, n, spans, first);
 
   // 16 bytes of columns per lane where every row of X and Y begins on 16 bytes and k is whole vectors; else one column
@@ -295,32 +324,41 @@ static int mm_spmm(sbx_handle_t h, int64_t n, int64_t m, int64_t nnz, int64_t k,
   const int64_t blocks = (lanes + 63) / 64;      // blocks of columns (the grid's second dimension; at most 2^14)
   const int G = (int)((lanes + blocks - 1) / blocks);  // lanes of a group: the blocks are equal up to one lane
   const dim3 grid((unsigned)spans, (unsigned)blocks);
-#define MM_LAUNCH(VEC, WIDE)                                                                                           \
-  SBX_KLAUNCH(h, SBX_K_SPMM, (k_spmm_span<I, N, V, VEC, WIDE>), grid, dim3(64), (const N *)row_ptr, (const I *)col,    \
-              (const V *)val, (const V *)x, ldx, m, nnz, k, G, ((uintptr_t)col & 15) == 0, ((uintptr_t)val & 15) == 0,         \
+  const bool gather = perm != nullptr && val != nullptr;  // (a pattern has nothing to gather: the plain kernel)
+#define MM_LAUNCH_P(VEC, WIDE, PERM, VAL_VEC)                                                                          \
+  SBX_KLAUNCH(h, kid, (k_spmm_span<I, N, V, VEC, WIDE, PERM>), grid, dim3(64), (const N *)row_ptr, (const I *)col,     \
+              (const N *)perm, (const V *)val, (const V *)x, ldx, m, nnz, k, G, ((uintptr_t)col & 15) == 0, VAL_VEC,   \
               (const int64_t *)first, (V *)y, ldy, trow, tsum)
+#define MM_LAUNCH(VEC, WIDE)                                                       \
+  do {                                                                             \
+    if (gather) MM_LAUNCH_P(VEC, WIDE, true, ((uintptr_t)perm & 15) == 0);         \
+    else MM_LAUNCH_P(VEC, WIDE, false, ((uintptr_t)val & 15) == 0);                \
+  } while (0)
   if (64 / G == 1) {
     if (vec) MM_LAUNCH(W, true); else MM_LAUNCH(1, true);
   } else {
     if (vec) MM_LAUNCH(W, false); else MM_LAUNCH(1, false);
   }
 #undef MM_LAUNCH
-  SBX_KLAUNCH(h, SBX_K_SPMM, (k_spmm_carry<V>), dim3((unsigned)((spans * k + MM - 1) / MM)), dim3(MM),
+#undef MM_LAUNCH_P
+  SBX_KLAUNCH(h, kid, (k_spmm_carry<V>), dim3((unsigned)((spans * k + MM - 1) / MM)), dim3(MM),
               (const int64_t *)trow, (const V *)tsum, spans, k, (V *)y, ldy);
   SBX_LAUNCH_CHECK(h);
-  SBX_PROF_BYTES(h, SBX_K_SPMM, nnz * (int64_t)(sizeof(I) + (val ? sizeof(V) : 0)) + n * (int64_t)sizeof(N) +
+  SBX_PROF_BYTES(h, kid, nnz * (int64_t)(sizeof(I) + (val ? sizeof(V) : 0) + (gather ? sizeof(N) : 0)) + n * (int64_t)sizeof(N) +
                                     (m + n) * k * (int64_t)sizeof(V));
   return SBX_OK;
 }
 
 template <typename I, typename N>
 static int mm_spmm_v(sbx_handle_t h, sbx_value_type vt, int64_t n, int64_t m, int64_t nnz, int64_t k, const void *row_ptr,
-                     const void *col, const void *val, const void *x, int64_t ldx, void *y, int64_t ldy) {
+                     const void *col, const void *val, const void *x, int64_t ldx, void *y, int64_t ldy,
+                     const void *perm = nullptr, int kid = SBX_K_SPMM) {
   switch (vt) {
-    case SBX_V_F32: return mm_spmm<I, N, float>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
-    case SBX_V_F64: return mm_spmm<I, N, double>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
-    case SBX_V_I32: case SBX_V_U32: return mm_spmm<I, N, uint32_t>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
-    default: return mm_spmm<I, N, uint64_t>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);  // SBX_V_I64, SBX_V_U64
+    case SBX_V_F32: return mm_spmm<I, N, float>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy, perm, kid);
+    case SBX_V_F64: return mm_spmm<I, N, double>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy, perm, kid);
+    case SBX_V_I32: case SBX_V_U32:
+      return mm_spmm<I, N, uint32_t>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy, perm, kid);
+    default: return mm_spmm<I, N, uint64_t>(h, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy, perm, kid);  // I64, U64
   }
 }
 
@@ -351,4 +389,35 @@ extern "C" int sbmm_csr_spmm(sbx_handle_t h, sbx_index_type it, sbx_value_type v
   if (it == SBX_I32) return mm_spmm_v<int32_t, int32_t>(h, vt, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
   if (it == SBX_I32_N64) return mm_spmm_v<int32_t, int64_t>(h, vt, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
   return mm_spmm_v<int64_t, int64_t>(h, vt, n, m, nnz, k, row_ptr, col, val, x, ldx, y, ldy);
+}
+
+// Y = A^T X from a plan (include/sbmt.h): sbmm_csr_spmm of the m x n matrix (col_ptr, row) with every value read through
+// perm inside the span kernel.  One column at unit strides stays on the span kernel too: the SpMV has no indirection.
+extern "C" int sbmt_csr_spmm_t(sbx_handle_t h, sbx_index_type it, sbx_value_type vt, int64_t n, int64_t m, int64_t nnz,
+                               int64_t k, const void *col_ptr, const void *row, const void *perm, const void *val,
+                               const void *x, int64_t ldx, void *y, int64_t ldy) {
+  if (!h) return SBX_ERR_BAD_ARG;
+  SBX_REQUIRE(h, n >= 0, "n is negative");
+  SBX_REQUIRE(h, m >= 0, "m is negative");
+  SBX_REQUIRE(h, nnz >= 0, "nnz is negative");
+  SBX_REQUIRE(h, k >= 0, "k is negative");
+  SBX_REQUIRE(h, ldx >= k, "ldx is below k");
+  SBX_REQUIRE(h, ldy >= k, "ldy is below k");
+  SBX_REQUIRE(h, m > 0 || nnz == 0, "nnz > 0 with m == 0");
+  SBX_REQUIRE(h, col_ptr != nullptr || m == 0, "col_ptr is NULL");
+  SBX_REQUIRE(h, row != nullptr || nnz == 0, "row is NULL");
+  SBX_REQUIRE(h, perm != nullptr || val == nullptr || nnz == 0, "perm is NULL");
+  SBX_REQUIRE(h, x != nullptr || n == 0 || nnz == 0, "x is NULL");
+  SBX_REQUIRE(h, y != nullptr || m == 0, "y is NULL");
+  SBX_REQUIRE(h, it == SBX_I32 || it == SBX_I64 || it == SBX_I32_N64, "unknown index type");
+  SBX_REQUIRE(h, vt != SBX_V_NONE && sbx_value_bytes(vt) > 0, "the value type must be one of F32, F64, I32, U32, I64, U64");
+  if (k > ((int64_t)1 << 20)) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: k = %lld > 2^20", __func__, (long long)k);
+  if (nnz >= ((int64_t)1 << 42)) SBX_FAIL(h, SBX_ERR_UNSUPPORTED, "%s: nnz = %lld >= 2^42", __func__, (long long)nnz);
+  if (m == 0 || k == 0) return SBX_OK;
+  const void *pm = val ? perm : nullptr;  // (a pattern never reads perm)
+  if (it == SBX_I32)
+    return mm_spmm_v<int32_t, int32_t>(h, vt, m, n, nnz, k, col_ptr, row, val, x, ldx, y, ldy, pm, SBX_K_SPMM_T);
+  if (it == SBX_I32_N64)
+    return mm_spmm_v<int32_t, int64_t>(h, vt, m, n, nnz, k, col_ptr, row, val, x, ldx, y, ldy, pm, SBX_K_SPMM_T);
+  return mm_spmm_v<int64_t, int64_t>(h, vt, m, n, nnz, k, col_ptr, row, val, x, ldx, y, ldy, pm, SBX_K_SPMM_T);
 }

@@ -7,6 +7,7 @@
 //                                              no kernel call of the canonical pipeline pays a trip over PCIe
 //   SpMV<I, N, V, F>                           the KernelFunction: y = A x on the device (kernels/spmv.h)
 //   SpMM<I, N, V, F>                           the KernelFunction: Y = A X for k columns on the device (kernels/spmm.h)
+//   SpMMTransposed<I, N, V, F>                 the KernelFunction: Y = A^T X from a plan (kernels/spmm_transposed.h)
 //   SDDMM<I, N, V, F>                          the KernelFunction: out = vals (.) (U V^T) on A's pattern (kernels/sddmm.h)
 //   RowSoftmax<I, N, V, F>                     the KernelFunction: the softmax of every row's values (kernels/row_softmax.h)
 //
@@ -28,6 +29,7 @@
 #include "sparsebase/kernels/row_softmax.h"
 #include "sparsebase/kernels/sddmm.h"
 #include "sparsebase/kernels/spmm.h"
+#include "sparsebase/kernels/spmm_transposed.h"
 #include "sparsebase/kernels/spmv.h"
 
 namespace sparsebase::experiment {
@@ -184,6 +186,57 @@ std::any SpMM(DataMap &data, std::any &fparams, std::any &pparams, std::any &kpa
   const size_t count = (size_t)v.n * params->k;
   hip::Staged<FloatType> d_y(*v.dev, count ? count : 1);
   kernels::detail::MultiplyBlock(v, x, params->k, has_vals ? &vals : nullptr, d_y.get());
+  FloatType *y = new FloatType[count ? count : 1];
+  try {
+    d_y.ToHost(y);  // (a blocking copy behind the kernels on the handle's stream: the synchronise)
+  } catch (...) {
+    delete[] y;
+    throw;
+  }
+  return y;
+}
+
+// The kernel parameter of SpMMTransposed: the number of columns of X, optionally the values (an Array<FloatType> or an
+// HIPArray<FloatType> in the matrix's CSR order; empty: a pattern, the plan holds no values) and optionally a plan, a
+// std::shared_ptr<kernels::TransposePlan<IDType, NNZType>> built from the format the kernel will see (empty: the plan is
+// built inside every call, a sort of all stored entries inside the harness's timing).
+struct SpMMTransposedParams {
+  size_t k = 1;
+  std::any vals;
+  std::any plan;
+};
+
+// The SpMMTransposed KernelFunction, with SpMM's contract: data["processed_format"] is a CSR or an HIPCSR of <IDType,
+// NNZType, ValueType>; fparams holds X, n * k values row-major, as an Array<FloatType> or an HIPArray<FloatType>; kparams
+// holds an SpMMTransposedParams.  The result is a host FloatType* of m * k values from new[], owned by the caller,
+// returned after the device has finished.
+template <typename IDType, typename NNZType, typename ValueType, typename FloatType>
+std::any SpMMTransposed(DataMap &data, std::any &fparams, std::any &pparams, std::any &kparams) {
+  typedef kernels::TransposePlan<IDType, NNZType> Plan;
+  auto *params = std::any_cast<SpMMTransposedParams>(&kparams);
+  if (!params) throw utils::TypeException("experiment::SpMMTransposed: the kernel's parameter must be an SpMMTransposedParams");
+  std::shared_ptr<Plan> plan;
+  if (params->plan.has_value()) {
+    auto *given = std::any_cast<std::shared_ptr<Plan>>(&params->plan);
+    if (!given || !*given)
+      throw utils::TypeException("experiment::SpMMTransposed: the plan must be a shared_ptr to a TransposePlan of the kernel's index types");
+    plan = *given;
+  } else {
+    format::Format *A = data.at("processed_format");
+    if (A->template IsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>())
+      plan = std::make_shared<Plan>(A->template AsAbsolute<format::HIPCSR<IDType, NNZType, ValueType>>());
+    else
+      plan = std::make_shared<Plan>(A->template AsAbsolute<format::CSR<IDType, NNZType, ValueType>>());
+  }
+  hip::Device &dev = plan->device();
+  auto x = detail::OperandOf<FloatType>(fparams, dev, "experiment::SpMMTransposed: ", "X (the file's parameter)");
+  const bool has_vals = params->vals.has_value();
+  kernels::detail::DeviceVector<FloatType> vals;
+  if (has_vals)
+    vals = detail::OperandOf<FloatType>(params->vals, dev, "experiment::SpMMTransposed: ", "the values (the kernel's parameter)");
+  const size_t count = (size_t)plan->columns() * params->k;
+  hip::Staged<FloatType> d_y(dev, count ? count : 1);
+  kernels::detail::MultiplyTransposed(*plan, x, params->k, has_vals ? &vals : nullptr, d_y.get());
   FloatType *y = new FloatType[count ? count : 1];
   try {
     d_y.ToHost(y);  // (a blocking copy behind the kernels on the handle's stream: the synchronise)

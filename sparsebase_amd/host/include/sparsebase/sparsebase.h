@@ -40,6 +40,7 @@
 #include "sparsebase/kernels/row_softmax.h"
 #include "sparsebase/kernels/sddmm.h"
 #include "sparsebase/kernels/spmm.h"
+#include "sparsebase/kernels/spmm_transposed.h"
 #include "sparsebase/kernels/spmv.h"
 #include "sparsebase/reorder/boba_reorder.h"
 #include "sparsebase/reorder/reorder_heatmap.h"

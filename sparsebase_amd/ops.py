@@ -1,5 +1,5 @@
 """Tensor-level plumbing over the C ABI (include/sbx.h, sbx_text.h, sbx_stats.h, sbio.h, sbgr.h, sbhg.h, sbfx.h, sbsym.h, sbmv.h, sbmm.h,
-sbdd.h, sbsm.h).
+sbdd.h, sbsm.h, sbmt.h).
 
 torch owns the device buffers and the stream; every function here only
 marshals pointers into libsbx.so.  Nothing in this module computes on the CPU:
@@ -7,6 +7,7 @@ if the HIP library or a GPU is missing the calls raise.
 """
 import ctypes as C
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -627,6 +628,136 @@ class _RowSoftmax(torch.autograd.Function):
 def csr_row_softmax_autograd(row_ptr, val):
     """csr_row_softmax as a differentiable function of val: the backward is one call of csr_row_softmax_backward."""
     return _RowSoftmax.apply(row_ptr, val)
+
+
+# ----------------------------------------------------------------------------- Y = A^T X from a plan (include/sbmt.h)
+class TransposePlan(NamedTuple):
+    """The pattern of the transpose of an n x m CSR matrix and where each of its entries lies in the CSR arrays: three
+    device tensors that depend on (row_ptr, col) alone.  Values never enter: one plan serves every val."""
+    n: int
+    m: int
+    col_ptr: torch.Tensor  # m + 1 offsets, the dtype of row_ptr
+    row: torch.Tensor      # nnz row ids, the dtype of col
+    perm: torch.Tensor     # nnz positions in the CSR arrays, the dtype of row_ptr
+
+
+def csr_transpose_plan(row_ptr, col, m):
+    """TransposePlan(n, m, col_ptr, row, perm) of a CSR matrix with m columns: perm is the stable order of the stored
+    entries by column, (col_ptr, row) the CSR arrays of the transpose.  Synchronous; a column outside [0, m) raises.  See
+    sbmt_csr_transpose_plan in include/sbmt.h."""
+    hd = handle_for(_check_dev(row_ptr, col))
+    if row_ptr.dim() != 1 or row_ptr.numel() < 1 or col.dim() != 1:
+        raise ValueError("row_ptr must be 1-D with n + 1 offsets and col 1-D")
+    n, m, nnz = row_ptr.numel() - 1, int(m), col.numel()
+    cp = torch.empty(m + 1, dtype=row_ptr.dtype, device=row_ptr.device)
+    ro = torch.empty_like(col)
+    pm = torch.empty(nnz, dtype=row_ptr.dtype, device=row_ptr.device)
+    hd.check(hd.lib.sbmt_csr_transpose_plan(hd.h, _it(row_ptr, col), n, m, nnz, _p(row_ptr), _p(col), _p(cp), _p(ro), _p(pm)))
+    return TransposePlan(n, m, cp, ro, pm)
+
+
+def csr_spmm_t(plan, X, val=None, out=None):
+    """Y = A^T X from a TransposePlan: a device tensor of m x k values of X's dtype (float32, float64, int32 or int64;
+    integers wrap).  X is (n, k), 2-D with stride(1) == 1 (a column slice of a wider tensor is fine), as is `out`.  val
+    holds the matrix's values in CSR order, as csr_spmm takes them; val=None is a pattern matrix.  Deterministic and
+    asynchronous; for k >= 2 the bits are those of csr_spmm on the materialised transpose.  See sbmt_csr_spmm_t in
+    include/sbmt.h."""
+    dev = _check_dev(plan.col_ptr, plan.row, plan.perm, val)
+    _check_rows(X, "X")
+    if out is not None:
+        _check_rows(out, "out")
+    if X.device != dev or (out is not None and out.device != dev):
+        raise ValueError("all tensors must live on the same device")
+    n, m, k, nnz = int(plan.n), int(plan.m), int(X.shape[1]), plan.row.numel()
+    if plan.col_ptr.numel() != m + 1 or plan.perm.numel() != nnz or plan.perm.dtype != plan.col_ptr.dtype:
+        raise ValueError("the plan needs m + 1 offsets and one position, of the offsets' dtype, per stored entry")
+    if n > X.shape[0]:
+        raise ValueError(f"X holds {X.shape[0]} rows, the matrix has {n}")
+    if val is not None and (val.dtype != X.dtype or val.dim() != 1 or val.numel() != nnz):
+        raise TypeError("val must be 1-D with the dtype of X and one value per stored entry")
+    y = torch.empty((m, k), dtype=X.dtype, device=X.device) if out is None else out
+    if y.dtype != X.dtype or tuple(y.shape) != (m, k):
+        raise TypeError("out must have the dtype of X, one row per column of the matrix and one column per column of X")
+    hd = handle_for(dev)
+    hd.check(hd.lib.sbmt_csr_spmm_t(hd.h, _it(plan.col_ptr, plan.row), _vt(X), n, m, nnz, k, _p(plan.col_ptr), _p(plan.row),
+                                    _p(plan.perm), _p(val), _p(X), _ld(X), _p(y), _ld(y)))
+    return y
+
+
+class _SpMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, row_ptr, col, val, X, plan):
+        Xd = X.detach()
+        vd = None if val is None else val.detach().contiguous()
+        ctx.save_for_backward(row_ptr, col, vd, Xd)
+        ctx.plan = plan
+        return csr_spmm(row_ptr, col, Xd, val=vd, m=plan.m)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        row_ptr, col, val, X = ctx.saved_tensors
+        g = g.contiguous()
+        dval = dX = None
+        if val is not None and ctx.needs_input_grad[2]:
+            dval = csr_sddmm(row_ptr, col, g, X)
+        if ctx.needs_input_grad[3]:
+            dX = csr_spmm_t(ctx.plan, g, val)
+        return None, None, dval, dX, None
+
+
+def csr_spmm_autograd(row_ptr, col, val, X, plan=None, m=None):
+    """csr_spmm as a differentiable function of val and X: the backward is dval = csr_sddmm(row_ptr, col, dY, X) (the
+    pattern form: no values) and dX = csr_spmm_t(plan, dY, val), each computed only where a gradient is asked for.
+    val=None is a pattern matrix and has no gradient.  plan=None builds the TransposePlan on every call, a sort of all
+    stored entries: a training loop builds it once with csr_transpose_plan(row_ptr, col, m) and passes it.  Not twice
+    differentiable."""
+    if plan is None:
+        plan = csr_transpose_plan(row_ptr, col, int(X.shape[0]) if m is None else int(m))
+    if plan.n != row_ptr.numel() - 1 or (m is not None and int(m) != plan.m):
+        raise ValueError("the plan is not one of this matrix")
+    if X.dim() == 2 and X.shape[0] > plan.m:  # (rows beyond the matrix's columns take no part and get a gradient of 0)
+        X = X[:plan.m]
+    return _SpMM.apply(row_ptr, col, val, X, plan)
+
+
+class _SDDMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, row_ptr, col, val, U, V, plan):
+        Ud, Vd = U.detach(), V.detach()
+        vd = None if val is None else val.detach().contiguous()
+        ctx.save_for_backward(row_ptr, col, vd, Ud, Vd)
+        ctx.plan = plan
+        return csr_sddmm(row_ptr, col, Ud, Vd, val=vd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        row_ptr, col, val, U, V = ctx.saved_tensors
+        g = g.contiguous()
+        dval = dU = dV = None
+        if val is not None and ctx.needs_input_grad[2]:
+            dval = csr_sddmm(row_ptr, col, U, V, val=g)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            w = g if val is None else g * val
+            if ctx.needs_input_grad[3]:
+                dU = csr_spmm(row_ptr, col, V, val=w)
+            if ctx.needs_input_grad[4]:
+                dV = csr_spmm_t(ctx.plan, U, val=w)
+        return None, None, dval, dU, dV, None
+
+
+def csr_sddmm_autograd(row_ptr, col, U, V, val=None, plan=None):
+    """csr_sddmm as a differentiable function of val, U and V.  With g the gradient of the output and w = g * val (w = g
+    for a pattern): dval = csr_sddmm(row_ptr, col, U, V, val=g), dU = csr_spmm(row_ptr, col, V, val=w) and
+    dV = csr_spmm_t(plan, U, val=w), each computed only where a gradient is asked for.  plan=None builds the
+    TransposePlan on every call: a training loop passes one (csr_transpose_plan(row_ptr, col, V.shape[0])).  Not twice
+    differentiable."""
+    if plan is None:
+        plan = csr_transpose_plan(row_ptr, col, int(V.shape[0]))
+    if plan.n != row_ptr.numel() - 1 or plan.m != int(V.shape[0]):
+        raise ValueError("the plan is not one of this matrix")
+    return _SDDMM.apply(row_ptr, col, val, U, V, plan)
 
 
 def slashburn_reorder(row_ptr, col, k, greedy=False, hub_order=False, out=None, return_stats=False):
