@@ -36,11 +36,12 @@ def _check(rp, col, ks, flags=FLAGS, tups=tuple(TUPLES)):
     n = len(rp) - 1
     for k in ks:
         for greedy, hub_order in flags:
-            want = slashburn(rp, col, k, greedy, hub_order)
+            want, want_stats = slashburn(rp, col, k, greedy, hub_order, return_stats=True)
             for tup in tups:
-                got = _gpu(rp, col, k, greedy, hub_order, tup)
+                got, stats = _gpu(rp, col, k, greedy, hub_order, tup, stats=True)
                 assert np.array_equal(np.sort(got), np.arange(n)), (tup, k, greedy, hub_order)
                 assert np.array_equal(got, want), (tup, k, greedy, hub_order)
+                assert stats == want_stats, (tup, k, greedy, hub_order)  # all five of sbx_slashburn_stats
 
 
 @pytest.mark.parametrize("tup", list(TUPLES))

@@ -229,15 +229,14 @@ def _labels(srp, scol, alive):
     n = len(srp) - 1
     src = np.repeat(np.arange(n), np.diff(srp))
     ok = alive[src] & alive[scol]
-    a, b = src[ok], scol[ok]  # (grouped by source: S is row-major)
+    a, b = src[ok], scol[ok]
     lab = np.where(alive, np.arange(n), -1)
     if len(a) == 0:
         return lab
-    starts = np.flatnonzero(np.r_[True, a[1:] != a[:-1]])
-    heads = a[starts]
     while True:
+        # every label is a root here (lab[lab[v]] == lab[v]): hook each root under the smallest label next to its tree
         m = lab.copy()
-        m[heads] = np.minimum(m[heads], np.minimum.reduceat(lab[b], starts))
+        np.minimum.at(m, lab[a], lab[b])
         while True:  # pointer jumping: labels stay ids of the same component
             mm = np.where(alive, m[np.maximum(m, 0)], -1)
             if np.array_equal(mm, m):
@@ -256,19 +255,31 @@ def _members(lab, mask):
     return dict(zip(keys.tolist(), np.split(v[o], first[1:])))
 
 
-def _bfs_order(srp, scol, members, root):
-    """orderCC (:191-222): FIFO BFS over S limited to `members` from root, children in adjacency order."""
+def _bfs_levels(srp, scol, members, root):
+    """orderCC (:191-222): FIFO BFS over S limited to `members` from root, children in adjacency order; the order and
+    the width of every level.  A long row is cut to the first occurrence of each column first (a repeat is seen
+    already when its turn comes, so the order is the same)."""
     seen = {root}
-    out, q = [root], deque([root])
-    while q:
-        u = q.popleft()
-        for w in scol[srp[u]:srp[u + 1]]:
-            w = int(w)
-            if w in members and w not in seen:
-                seen.add(w)
-                out.append(w)
-                q.append(w)
-    return out
+    out, widths = [root], []
+    level = [root]
+    while level:
+        widths.append(len(level))
+        nxt = []
+        for u in level:
+            row = scol[srp[u]:srp[u + 1]]
+            if len(row) > 256:
+                row = row[np.sort(np.unique(row, return_index=True)[1])]
+            for w in row.tolist():
+                if w in members and w not in seen:
+                    seen.add(w)
+                    nxt.append(w)
+        out += nxt
+        level = nxt
+    return out, widths
+
+
+def _bfs_order(srp, scol, members, root):
+    return _bfs_levels(srp, scol, members, root)[0]
 
 
 def default_hubs(deg, elig, k):
@@ -298,32 +309,49 @@ def heap_hubs(deg, elig, k):
     return np.array([v for _, v in sorted(pq, reverse=True)], np.int64)
 
 
-def slashburn(rp, col, k, greedy=False, hub_order=False):
-    """The rules of include/sbx.h (sbx_slashburn_reorder): inv[old] = new."""
+def slashburn(rp, col, k, greedy=False, hub_order=False, return_stats=False, trace=None):
+    """The rules of include/sbx.h (sbx_slashburn_reorder): inv[old] = new.  return_stats: (inv, the five statistics of
+    sbx_slashburn_stats).  trace: a list that receives, per batch of components placed together (phase 0, then each
+    round), the level widths of the BFS from all of the batch's roots at once, W[0] = the number of roots."""
     n = len(rp) - 1
     srp, scol = sym_adjacency(rp, col, n)
     src = np.repeat(np.arange(n), np.diff(srp))
     pos = np.full(n, -1, np.int64)
     back = 0
+    stats = dict(rounds=0, hubs=0, spoke_components=0, initial_components=0, final_gcc=0)
+    batch = []
+
+    def done():
+        return (pos, stats) if return_stats else pos
 
     def place(members, root):
         nonlocal back
-        order = _bfs_order(srp, scol, members, root)
+        order, widths = _bfs_levels(srp, scol, members, root)
         assert len(order) == len(members)
         pos[np.asarray(order)] = n - 1 - back - np.arange(len(order))
         back += len(order)
+        batch.append(widths)
+
+    def end_batch():
+        if trace is not None and batch:
+            trace.append([sum(w[i] for w in batch if i < len(w)) for i in range(max(map(len, batch)))])
+        batch.clear()
 
     # phase 0
     lab = _labels(srp, scol, np.ones(n, bool))
     roots, sizes = np.unique(lab, return_counts=True)
     comps = sorted(zip(sizes.tolist(), roots.tolist()))
+    stats["initial_components"] = len(comps)
     groups = _members(lab, np.ones(n, bool))
     for size, root in comps[:-1]:
         place(set(groups[root].tolist()), root)
     g_size, g_root = comps[-1]
     if g_size < k:
         place(set(groups[g_root].tolist()), g_root)
-        return pos
+        end_batch()
+        stats["final_gcc"] = g_size
+        return done()
+    end_batch()
     E = lab == g_root
     t = 0
     while True:
@@ -342,6 +370,8 @@ def slashburn(rp, col, k, greedy=False, hub_order=False):
             hubs = default_hubs(deg, E, k)
         pos[hubs] = t * k + np.arange(k)
         E[hubs] = False
+        stats["rounds"] += 1
+        stats["hubs"] += k
         lab = _labels(srp, scol, E)
         # the scan: rows h_{k-1} .. h_0; each component's first entry is its root, that row's j its hub index
         scan_j = np.concatenate([np.full(srp[h + 1] - srp[h], j) for j, h in reversed(list(enumerate(hubs)))])
@@ -356,6 +386,7 @@ def slashburn(rp, col, k, greedy=False, hub_order=False):
         g = min(range(len(first_lab)), key=lambda i: (-size[i], first_at[i]))  # largest, then earliest root entry
         others = sorted((int(hub_j[i]) if hub_order else 0, int(size[i]), int(root[i]), int(first_lab[i]))
                         for i in range(len(first_lab)) if i != g)
+        stats["spoke_components"] += len(others)
         groups = _members(lab, E)
         for _, _, r, lb in others:
             members = groups[lb]
@@ -363,11 +394,14 @@ def slashburn(rp, col, k, greedy=False, hub_order=False):
             place(set(members.tolist()), r)
         if size[g] < k:
             place(set(groups[int(first_lab[g])].tolist()), int(root[g]))
+            end_batch()
+            stats["final_gcc"] = int(size[g])
             break
+        end_batch()
         E = lab == first_lab[g]
         t += 1
     assert (pos >= 0).all()
-    return pos
+    return done()
 
 
 # ---- graphs ----------------------------------------------------------------------------------------------------------
